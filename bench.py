@@ -21,13 +21,19 @@ verdict is broadcast
 (north_star: partials combined on the host).  value = total sets
 over all ranks / max-over-ranks time.
 
-Secondary legs (N = 1, after the timed region; reported, never `value`):
+A plain run does only what `value` needs: workload, warm-up, the K timed
+steps, the result line.  --dump-outputs DIR then writes what the last timed
+step returned to its caller (dump_outputs).
+
+--full adds everything else (reported, never `value`): the per-kernel timings
+of one call alone on the GPU (the dominant kernel's roofline is priced on
+them), idle and loaded p50 latencies and, at N = 1, the secondary legs:
 host-buffer API throughput (PCIe included), same-message gossip jobs (512
 jobs x 128 sets per call), an adversarial leg (one wrong-message set per call),
-the C1 CPU p50 of one 128-set job, p50 latency of one 128-set request on the
-GPU, the CPU baseline.
+the other BASELINE configs and the perf-suite sizes, the node leg, the C1 CPU
+p50 of one 128-set job, the CPU baseline.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -157,10 +163,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--sets", type=int, default=65536)
     ap.add_argument("--per-request", type=int, default=128)
-    ap.add_argument("--latency-reps", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is reported beside `value`: per-kernel "
+                         "iso timings, latency p50s, secondary / config / node legs, the CPU baseline (each can "
+                         "be trimmed with the options below; without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--latency-reps", type=int, default=10, help="with --full")
     ap.add_argument("--iso-reps", type=int, default=3,
-                    help="sync calls after the timed region whose stage times price the dominant kernel")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
+                    help="with --full: sync calls after the timed region whose stage times price the dominant kernel")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="skip the secondary legs (host API, same-message, ...)")
     ap.add_argument("--no-configs", action="store_true",
@@ -179,6 +191,12 @@ def main():
                     help="calls kept in flight (= library slots, env LB_SLOTS)")
     ap.add_argument("--node-data", help=argparse.SUPPRESS)  # (internal: the node leg's input child)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:
+        # a plain run: set-up, warm-up, the timed steps, the result line -- nothing else
+        a.latency_reps = a.iso_reps = 0
+        a.no_legs = a.no_configs = a.no_cpu_baseline = True
 
     if a.node_data:
         node_data_main(a.node_data, a.sets)
@@ -255,6 +273,7 @@ def main():
                                    d_valid[k % len(d_valid)].data_ptr(), d_err[k % len(d_err)].data_ptr())
 
     combined = {"checks": 0, "passed": 0, "partials_per_check": 0, "gather_ms": 0.0, "check_ms": 0.0}
+    last_call = {}  # the latest two-phase call's combined verdict (--dump-outputs)
 
     def resolve(t):
         """Two-phase step: this rank's partial, all ranks' partials gathered on the
@@ -281,6 +300,7 @@ def main():
         t3 = time.perf_counter()
         dev.finish_t(t, ok)
         dev.wait(t)
+        last_call["check"] = ok
         combined["checks"] += 1
         combined["passed"] += int(ok)
         combined["partials_per_check"] = len(partials)
@@ -372,6 +392,7 @@ def main():
                     with lock:
                         dev.wait(t)
                         accumulate()
+                    last_call["check"] = ok_t
                     combined["checks"] += 1
                     combined["passed"] += int(ok_t)
                     combined["partials_per_check"] = len(partials)
@@ -422,6 +443,10 @@ def main():
     used = sorted({k % len(d_valid) for k in range(a.steps)})
     ok = all(bool(d_valid[i].cpu().numpy().all()) for i in used) and \
         not any(bool(d_err[i].cpu().numpy().any()) for i in used)
+    if a.dump_outputs:
+        last = (a.steps - 1) % len(d_valid)  # the buffers the last timed step wrote
+        dump_outputs(a.dump_outputs, rank, d_valid[last].cpu().numpy(), d_err[last].cpu().numpy(),
+                     last_call if combine else {})
 
     # the same call, one at a time and on ONE stream (a context with LB_DAG=0: no kernel of
     # the other DAG branch and no other call beside it): every kernel's duration alone on the
@@ -568,6 +593,7 @@ def main():
         "n_gpus": world,
         "steps": a.steps,
         "warmup": a.warmup,
+        "full": a.full,
         "ms_per_step": round(elapsed / a.steps * 1e3, 3),
         "higher_is_better": True,
         "scaling": "weak",
@@ -612,6 +638,23 @@ def main():
     print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
+
+
+def dump_outputs(d, rank, valid, errors, last_call):
+    """--dump-outputs DIR: what the last timed step handed back to its caller, as float32
+    DIR/<name>.npy (rank r > 0: <name>_rank<r>.npy) -- `valid` and `errors`, one verdict and
+    one error code per request; for a two-phase step also `check`, the combined check's
+    verdict.  The workload is a function of the arguments alone, so two builds can be
+    compared array for array.  (The 576-byte partial itself is not written: it is one
+    representative of a class that only the final exponentiation makes unique, and its bytes
+    differ between two runs of the same build -- the MSM fills its buckets in the order of
+    its atomics, k_msm_scatter -- while the check on it does not.)"""
+    os.makedirs(d, exist_ok=True)
+    arrays = {"valid": valid, "errors": errors}
+    if last_call:
+        arrays["check"] = np.array([last_call["check"]])
+    for name, arr in arrays.items():
+        np.save(os.path.join(d, name + ("_rank%d" % rank if rank else "") + ".npy"), arr.astype(np.float32))
 
 
 # Algorithmic work priced at the lowest count the same kernel reaches (VERDICT r3: the
