@@ -305,10 +305,40 @@ int lb_gt_check(lb_ctx* ctx, uint32_t n, const uint8_t* partials576, int32_t* ou
 int lb_verify_requests_finish(lb_ctx* ctx, uint64_t ticket, int merged_ok);
 
 /*
+ * Same-message aggregation mode of a context (lb_verify_same_message*, below).
+ *   LB_SM_PLAIN      (default) each job's pubkeys and signatures are summed as they are, as the
+ *                    reference snapshot does (jobItemWorkReq, jobItem.ts:64-86).  A sender who
+ *                    controls two sets of a job can make two invalid signatures sig_0 + D and
+ *                    sig_1 - D pass: their sum verifies.
+ *   LB_SM_RANDOMIZED every set i of the call (0 <= i < n_sets, over the whole call) gets the
+ *                    scalar s_i = batch_scalar(seed, LB_SM_AGG_INDEX_FLAG | i) -- the call's DRBG,
+ *                    lb_batch_scalars' 64-bit values in their GLV form -- and a job of two or more
+ *                    sets is aggregated as PK_j = sum s_i pk_i, S_j = sum s_i sig_i (blst's
+ *                    aggregateWithRandomness): a passing aggregate implies every set of the job
+ *                    valid except with probability 2^-64.  A job of exactly one set is not
+ *                    multiplied.  The index flag keeps these scalars apart from the merged check's
+ *                    r_k (indices < n_sets); a call of n_sets >= 2^31 is refused with
+ *                    LB_ERR_INVALID_ARGUMENT in this mode.
+ * In both modes out_valid[i] of a job that took the fast path is 1 for every set; in the
+ * randomized mode that is, for every set of every job, the verdict of the set verified alone.
+ * lb_set_same_message_mode applies to calls submitted afterwards (a call in flight keeps the mode
+ * it was submitted with); a mode other than the two above, or a NULL ctx -> LB_ERR_INVALID_ARGUMENT,
+ * nothing changed.  lb_same_message_mode returns the mode (NULL ctx -> LB_ERR_INVALID_ARGUMENT).
+ * A context starts in LB_SM_RANDOMIZED when the environment has LB_SM_RANDOMIZED=1 at
+ * lb_create / lb_create_lane (the operator's switch), else in LB_SM_PLAIN.
+ */
+#define LB_SM_PLAIN 0u
+#define LB_SM_RANDOMIZED 1u
+#define LB_SM_AGG_INDEX_FLAG 0x80000000u
+int lb_set_same_message_mode(lb_ctx* ctx, uint32_t mode);
+int lb_same_message_mode(const lb_ctx* ctx);
+
+/*
  * verifySignatureSetsSameMessage for one job (<= 128 sets in the reference,
  * any n here): out_valid[i] per set.  Fast path: every signature validates,
- * aggregate pubkeys and signatures (plain sums, as the reference does) and
- * core-verify once; otherwise / on failure every set is core-verified alone.
+ * aggregate pubkeys and signatures (plain sums as the reference does, or the
+ * randomized sums of LB_SM_RANDOMIZED, by the context's mode) and core-verify
+ * once; otherwise / on failure every set is core-verified alone.
  * n == 0 -> nothing written (the reference returns []).
  */
 int lb_verify_same_message(lb_ctx* ctx, uint32_t n, const uint8_t* pubkeys /* n x 96 */,
@@ -321,8 +351,9 @@ int lb_verify_same_message(lb_ctx* ctx, uint32_t n, const uint8_t* pubkeys /* n 
  * attestation-data group, chunked to <= 128 sets by verifySignatureSetsSameMessage,
  * index.ts:218-242).  Job j = sets [job_offsets[j], job_offsets[j+1]) over
  * messages[32 j .. 32 j + 32).  Every signature is decoded and validated once
- * on the GPU, each job's pubkeys and signatures are summed (plain sums, as
- * jobItemWorkReq does, jobItem.ts:64-86) and all jobs' aggregated sets are
+ * on the GPU, each job's pubkeys and signatures are summed (LB_SM_PLAIN: plain
+ * sums, as jobItemWorkReq does, jobItem.ts:64-86; LB_SM_RANDOMIZED: each set
+ * times its scalar s_i, above) and all jobs' aggregated sets are
  * verified together as 1-set requests of one merged call; the sets of a job
  * whose aggregate fails (or that holds a signature failing
  * Signature.fromBytes(validate=true)) are re-verified each alone
@@ -354,6 +385,14 @@ int lb_verify_same_message_batch(lb_ctx* ctx, const lb_same_message_batch* batch
  * (BN/chain/bls/multithread/index.ts:362-519). */
 int lb_verify_same_message_batch_async(lb_ctx* ctx, const lb_same_message_batch* batch, uint8_t* out_valid,
                                        uint8_t* out_job_fast, uint64_t* out_ticket);
+/* Stage-level entry (like lb_hash_to_g2): the decode + aggregation of a package in the
+ * context's current mode, without the verification.  out_pk96: n_jobs x 96 and out_sig192:
+ * n_jobs x 192, the aggregated set of each job as it would enter the pipeline;
+ * out_job_bad[j] = 1 where the job is not aggregated (empty, a signature failing
+ * Signature.fromBytes(validate=true), a pubkey that fails to load, or an infinite
+ * aggregated key); the outputs of such a job are all zero bytes. */
+int lb_same_message_aggregates(lb_ctx* ctx, const lb_same_message_batch* batch, uint8_t* out_pk96,
+                               uint8_t* out_sig192, uint8_t* out_job_bad);
 
 /* Sum of n uncompressed pubkeys -> 96-byte uncompressed encoding.  n == 0 ->
  * LB_ERR_INVALID_ARGUMENT (EMPTY_AGGREGATE_ARRAY). *out_status = LB_SET_*. */

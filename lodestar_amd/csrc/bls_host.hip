@@ -100,6 +100,7 @@ struct SmState {
   int phase = 0;                     // 1: phase 1 in flight, 2: phase 2 (retries) in flight
   uint32_t nr = 0, retried_jobs = 0, fast_sets = 0;
   bool by_index = false;
+  uint32_t mode = LB_SM_PLAIN;       // the context's aggregation mode when the package was submitted
   uint32_t nj = 0, ns = 0;
   uint8_t* out_valid = nullptr;     // caller: n_sets verdicts
   uint8_t* out_job_fast = nullptr;  // caller (optional): n_jobs flags
@@ -323,6 +324,10 @@ struct lb_ctx {
   // same-message packages of at most LB_SM_DEC_MAX signatures decode them as round programs
   // (k_lp_dec; LB_SM_LP_DECODE=0: k_decode_sigs always)
   bool sm_lp_decode = true;
+  // same-message aggregation of the packages submitted from now on: LB_SM_PLAIN (plain sums, the
+  // reference snapshot's) or LB_SM_RANDOMIZED (sum s_i pk_i / sum s_i sig_i, k_smrand.hip);
+  // lb_set_same_message_mode, or LB_SM_RANDOMIZED=1 in the environment at lb_create
+  uint32_t sm_mode = LB_SM_PLAIN;
   // lone pipeline calls of at most LB_LP_DEC_MAX sets decode their signatures the same way
   // (LB_LP_DECODE=0: k_decode_sigs)
   bool lp_decode = true;
@@ -1424,7 +1429,7 @@ size_t scratch_per_queue(int device, uint32_t* out_lane_bytes) {
                            (const void*)k_level_wc,
                            (const void*)k_msm_buckets, (const void*)k_msm_bits<TPB>, (const void*)k_msm_bits<LB_MSM_BITS_TPB>,
                            (const void*)k_decode_sigs,
-                           (const void*)k_scalar_pk};
+                           (const void*)k_scalar_pk, (const void*)k_sm_rand_pk, (const void*)k_sm_rand_sig};
   size_t lane = 0;
   for (const void* k : kernels) {
     hipFuncAttributes a{};
@@ -1498,6 +1503,7 @@ static int create_ctx(int device, lb_ctx** out_ctx, bool lane) {
   if (const char* e = getenv("LB_WIDE_TAIL")) ctx->wide_tail = atoi(e) != 0;
   if (const char* e = getenv("LB_MSM_BITS_LP")) ctx->msm_bits_lp = atoi(e) != 0;
   if (const char* e = getenv("LB_SM_LP_DECODE")) ctx->sm_lp_decode = atoi(e) != 0;
+  if (const char* e = getenv("LB_SM_RANDOMIZED")) ctx->sm_mode = atoi(e) == 1 ? LB_SM_RANDOMIZED : LB_SM_PLAIN;
   if (const char* e = getenv("LB_LP_DECODE")) ctx->lp_decode = atoi(e) != 0;
   if (const char* e = getenv("LB_LP_HASH_FINISH")) ctx->lp_hash_finish = atoi(e) != 0;
   if (const char* e = getenv("LB_LP_LINES")) ctx->lp_lines = atoi(e) != 0;
@@ -2775,6 +2781,10 @@ int sm_validate(lb_ctx* ctx, const lb_same_message_batch* b) {
     ctx->err = "null pointer in lb_same_message_batch";
     return LB_ERR_INVALID_ARGUMENT;
   }
+  if (ctx->sm_mode == LB_SM_RANDOMIZED && ns >= LB_SM_AGG_INDEX_FLAG) {
+    ctx->err = "randomized same-message aggregation: n_sets must be below 2^31 (LB_SM_AGG_INDEX_FLAG)";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
   if (b->job_offsets[0] != 0 || b->job_offsets[nj] != ns || b->sig_offsets[0] != 0) {
     ctx->err = "job_offsets / sig_offsets must start at 0 (job_offsets end at n_sets)";
     return LB_ERR_INVALID_ARGUMENT;
@@ -2800,11 +2810,28 @@ size_t sm_phase2_bytes(const lb_ctx* ctx, uint32_t ns) {
   return pipeline_ws_bytes(ctx, ns, ns) + n * (2 * 4 + sizeof(g2j) + 1 + 32 + 4 + 4 + 2) + 16 * 256;
 }
 
-// Phase 1 on slot `sl` (already retired by the caller); the call stays busy
-// until finish_slot, which runs sm_complete.
-int sm_submit(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint8_t* out_valid, uint8_t* out_job_fast) {
+// What the front of phase 1 (sm_front: staging, upload, decode, aggregation) leaves for the
+// verification of the aggregated sets (sm_submit) or for lb_same_message_aggregates.
+struct SmFront {
+  bool by_index = false;
+  size_t in_bytes = 0, res_bytes = 0;
+  char* h = nullptr;  // the slot's pinned staging: inputs, then results
+  const uint32_t* h_joff = nullptr;
+  const uint8_t *d_pks = nullptr, *d_msgs = nullptr, *d_seed = nullptr, *d_rows = nullptr;
+  const uint32_t *d_areq = nullptr, *d_asig = nullptr;
+  g2j* d_sig = nullptr;
+  uint8_t *d_sst = nullptr, *d_jpkst = nullptr, *d_pk96 = nullptr, *d_sig192 = nullptr, *d_jbad = nullptr;
+};
+
+// The front of phase 1 on slot `sl` (already retired by the caller), in aggregation mode `mode`:
+// the package staged and uploaded, every signature decoded + validated once, each job's
+// aggregated set in d_pk96 / d_sig192 with its flags d_jbad / d_jpkst.  pin_extra / ws_extra:
+// what the caller needs of the slot's staging and workspace after it (ws: the bump after it).
+int sm_front(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint32_t mode, size_t pin_extra, size_t ws_extra,
+             Bump& ws, SmFront& f) {
   const uint32_t nj = b->n_jobs, ns = b->n_sets;
   const bool by_index = b->pubkey_indices != nullptr;
+  const bool randomized = mode == LB_SM_RANDOMIZED;
   // mixed package (indices AND rows): rows of `pubkeys` named by flagged indices, as in
   // lb_request_batch (every row < n_rows is staged)
   size_t n_rows = 0;
@@ -2820,13 +2847,13 @@ int sm_submit(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint8_t* ou
   const size_t in_bytes = al256(sz_joff) + al256(sz_pk) + al256(sz_sigo) + al256(sz_sig) + al256(sz_msg) +
                           al256(sz_seed) + al256(sz_areq) + al256(sz_asig) + al256(sz_rows);
   const size_t ns1 = ns ? ns : 1;
-  const size_t res_bytes = 4 * al256(nj), retry_bytes = 2 * al256(4 * ns1) + 2 * al256(ns1);
+  const size_t res_bytes = 4 * al256(nj);
   const size_t extra = ns1 * (sizeof(g2j) + 1) + (size_t)nj * (sizeof(g1j) + 1 + 96 + 192 + 1 + 2) + 16 * 256;
-  LB_TRY(ensure_pin(ctx, sl, in_bytes + res_bytes + retry_bytes));
+  LB_TRY(ensure_pin(ctx, sl, in_bytes + res_bytes + pin_extra));
   // (+ a small package's decode records: 4 + 2 records, 5 flags and a status per signature)
   const size_t dec_bytes = ns <= LB_SM_DEC_MAX ? (size_t)ns * (6 * 64 + 5 * 4 + 1) + 6 * 256 : 0;
-  LB_TRY(ensure_ws(ctx, sl, in_bytes + extra + pipeline_ws_bytes(ctx, nj, nj) + sm_phase2_bytes(ctx, ns) + dec_bytes));
-  Bump ws{sl.d_ws, 0, sl.ws_cap};
+  LB_TRY(ensure_ws(ctx, sl, in_bytes + extra + ws_extra + dec_bytes));
+  ws = Bump{sl.d_ws, 0, sl.ws_cap};
   char* h = sl.h_pin;
   size_t ho = 0;
   auto stage = [&](const void* src, size_t n) {
@@ -2871,10 +2898,18 @@ int sm_submit(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint8_t* ou
   uint8_t* d_pk96 = ws.take<uint8_t>((size_t)nj * 96);
   uint8_t* d_sig192 = ws.take<uint8_t>((size_t)nj * 192);
   uint8_t* d_jbad = ws.take<uint8_t>(nj);
-  uint8_t* d_valid = ws.take<uint8_t>(nj);
-  uint8_t* d_err = ws.take<uint8_t>(nj);
   LB_TRY(begin_call(ctx, sl));
   LB_HIP(hipMemcpyAsync(d_in, h, in_bytes, hipMemcpyHostToDevice, sl.st[0]));
+  const PkSource src{by_index ? d_rows : d_pks, by_index ? (const uint32_t*)d_pks : nullptr, ctx->d_table,
+                     ctx->table_n};
+  const uint32_t agg_grid = nj < 16384u ? nj : 16384u;
+  // randomized sums: the G1 side needs only the upload, so with a second stream it runs there,
+  // beside the decode and the G2 side (joined below, before the aggregated sets are read)
+  const int pk_st = randomized && sl.st[1] != sl.st[0] ? 1 : 0;
+  if (randomized) {
+    if (pk_st) LB_TRY(stream_wait(ctx, sl, 0, 1, 5));
+    LB_STAGE("sm_rand_pk", pk_st, k_sm_rand_pk, agg_grid, TPB, nj, d_joff, src, d_seed, d_jpk, d_jpkst, d_pk96);
+  }
   if (ns && ns <= LB_SM_DEC_MAX && ctx->sm_lp_decode) {
     // a small package: each signature's decode as a round program on an 8-row workgroup (~540
     // rounds) instead of k_decode_sigs' one-lane chain (~4 ms); the same outputs and statuses
@@ -2899,13 +2934,56 @@ int sm_submit(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint8_t* ou
     LB_STAGE("sm_decode", 0, k_decode_sigs, blocks_for(ns), TPB, ns, d_sigs, d_sigo, (const uint8_t*)nullptr, d_sig,
              d_sst);
   }
-  const PkSource src{by_index ? d_rows : d_pks, by_index ? (const uint32_t*)d_pks : nullptr, ctx->d_table,
-                     ctx->table_n};
-  const uint32_t agg_grid = nj < 16384u ? nj : 16384u;
-  LB_STAGE("sm_pubkeys", 0, k_pubkeys_single, blocks_for(nj), TPB, nj, src, d_joff, d_jpk, d_jpkst);
-  LB_STAGE("sm_pubkeys_agg", 0, k_pubkeys_agg, agg_grid, TPB, nj, src, d_joff, d_jpk, d_jpkst);
-  LB_STAGE("sm_aggregate", 0, k_same_message_agg, agg_grid, TPB, nj, d_joff, (const g2j*)d_sig, (const uint8_t*)d_sst,
-           (const g1j*)d_jpk, d_pk96, d_sig192, d_jbad);
+  if (randomized) {
+    LB_STAGE("sm_rand_sig", 0, k_sm_rand_sig, agg_grid, TPB, nj, d_joff, d_seed, (const g2j*)d_sig,
+             (const uint8_t*)d_sst, d_sig192, d_jbad);
+    if (pk_st) LB_TRY(stream_wait(ctx, sl, 1, 0, 6));
+  } else {
+    LB_STAGE("sm_pubkeys", 0, k_pubkeys_single, blocks_for(nj), TPB, nj, src, d_joff, d_jpk, d_jpkst);
+    LB_STAGE("sm_pubkeys_agg", 0, k_pubkeys_agg, agg_grid, TPB, nj, src, d_joff, d_jpk, d_jpkst);
+    LB_STAGE("sm_aggregate", 0, k_same_message_agg, agg_grid, TPB, nj, d_joff, (const g2j*)d_sig,
+             (const uint8_t*)d_sst, (const g1j*)d_jpk, d_pk96, d_sig192, d_jbad);
+  }
+  f.by_index = by_index;
+  f.in_bytes = in_bytes;
+  f.res_bytes = res_bytes;
+  f.h = h;
+  f.h_joff = h_joff;
+  f.d_pks = d_pks;
+  f.d_msgs = d_msgs;
+  f.d_seed = d_seed;
+  f.d_rows = d_rows;
+  f.d_areq = d_areq;
+  f.d_asig = d_asig;
+  f.d_sig = d_sig;
+  f.d_sst = d_sst;
+  f.d_jpkst = d_jpkst;
+  f.d_pk96 = d_pk96;
+  f.d_sig192 = d_sig192;
+  f.d_jbad = d_jbad;
+  return LB_OK;
+}
+
+// Phase 1 on slot `sl` (already retired by the caller); the call stays busy
+// until finish_slot, which runs sm_complete.
+int sm_submit(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint8_t* out_valid, uint8_t* out_job_fast) {
+  const uint32_t nj = b->n_jobs, ns = b->n_sets;
+  const uint32_t mode = ctx->sm_mode;  // read once: the call keeps it whatever the context does later
+  const size_t ns1 = ns ? ns : 1;
+  const size_t retry_bytes = 2 * al256(4 * ns1) + 2 * al256(ns1);
+  Bump ws{nullptr, 0, 0};
+  SmFront f;
+  LB_TRY(sm_front(ctx, sl, b, mode, retry_bytes, pipeline_ws_bytes(ctx, nj, nj) + sm_phase2_bytes(ctx, ns), ws, f));
+  const bool by_index = f.by_index;
+  const size_t in_bytes = f.in_bytes, res_bytes = f.res_bytes;
+  char* h = f.h;
+  const uint32_t* h_joff = f.h_joff;
+  const uint8_t *d_pks = f.d_pks, *d_msgs = f.d_msgs, *d_seed = f.d_seed, *d_rows = f.d_rows;
+  const uint32_t *d_areq = f.d_areq, *d_asig = f.d_asig;
+  g2j* d_sig = f.d_sig;
+  uint8_t *d_sst = f.d_sst, *d_jpkst = f.d_jpkst, *d_pk96 = f.d_pk96, *d_sig192 = f.d_sig192, *d_jbad = f.d_jbad;
+  uint8_t* d_valid = ws.take<uint8_t>(nj);
+  uint8_t* d_err = ws.take<uint8_t>(nj);
   LB_TRY(run_pipeline(ctx, sl, nj, nj, d_areq, d_pk96, nullptr, nullptr, d_msgs, d_sig192, d_asig, d_seed, d_valid,
                       d_err, nullptr, ws));
   char* h_res = h + in_bytes;
@@ -2917,6 +2995,7 @@ int sm_submit(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint8_t* ou
   m.active = true;
   m.phase = 1;
   m.by_index = by_index;
+  m.mode = mode;
   m.nj = nj;
   m.ns = ns;
   m.out_valid = out_valid;
@@ -3105,6 +3184,53 @@ int lb_verify_same_message(lb_ctx* ctx, uint32_t n, const uint8_t* pks, const ui
   uint8_t fast = 0;
   LB_TRY(lb_verify_same_message_batch(ctx, &b, out_valid, &fast, nullptr));
   if (out_used_fast_path) *out_used_fast_path = fast;
+  return LB_OK;
+}
+
+int lb_set_same_message_mode(lb_ctx* ctx, uint32_t mode) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  if (mode != LB_SM_PLAIN && mode != LB_SM_RANDOMIZED) {
+    ctx->err = "lb_set_same_message_mode: LB_SM_PLAIN or LB_SM_RANDOMIZED";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  ctx->sm_mode = mode;
+  return LB_OK;
+}
+
+int lb_same_message_mode(const lb_ctx* ctx) { return ctx ? (int)ctx->sm_mode : LB_ERR_INVALID_ARGUMENT; }
+
+// Stage-level: the front of phase 1 alone (decode + aggregation in the context's mode) on the
+// idle slot 0, the jobs' aggregated sets copied out.
+int lb_same_message_aggregates(lb_ctx* ctx, const lb_same_message_batch* b, uint8_t* out_pk96, uint8_t* out_sig192,
+                               uint8_t* out_job_bad) {
+  if (!ctx || !b || (b->n_jobs && (!out_pk96 || !out_sig192 || !out_job_bad))) return LB_ERR_INVALID_ARGUMENT;
+  if (b->n_jobs == 0) return LB_OK;
+  LB_TRY(sm_validate(ctx, b));
+  LB_HIP(hipSetDevice(ctx->device));
+  LB_TRY(helper_slot(ctx));
+  Slot& sl = ctx->slots[0];
+  const uint32_t nj = b->n_jobs;
+  Bump ws{nullptr, 0, 0};
+  SmFront f;
+  LB_TRY(sm_front(ctx, sl, b, ctx->sm_mode, 0, 0, ws, f));
+  if (ws.off > ws.cap) {
+    ctx->err = "workspace overflow";
+    return LB_ERR_OUT_OF_MEMORY;
+  }
+  uint8_t* h_res = (uint8_t*)f.h + f.in_bytes;  // job_bad, pk status (al256(nj) each)
+  LB_HIP(hipMemcpyAsync(h_res, f.d_jbad, nj, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_HIP(hipMemcpyAsync(h_res + al256(nj), f.d_jpkst, nj, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_HIP(hipMemcpyAsync(out_pk96, f.d_pk96, (size_t)nj * 96, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_HIP(hipMemcpyAsync(out_sig192, f.d_sig192, (size_t)nj * 192, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_HIP(hipStreamSynchronize(sl.st[0]));
+  for (uint32_t j = 0; j < nj; j++) {
+    const bool bad = h_res[j] || h_res[al256(nj) + j] != LB_ST_OK;
+    out_job_bad[j] = bad ? 1 : 0;
+    if (bad) {
+      memset(out_pk96 + (size_t)j * 96, 0, 96);
+      memset(out_sig192 + (size_t)j * 192, 0, 192);
+    }
+  }
   return LB_OK;
 }
 

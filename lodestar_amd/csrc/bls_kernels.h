@@ -233,6 +233,18 @@ __global__ void __launch_bounds__(TPB) k_same_message_agg(uint32_t n_jobs, const
                                                           const g1j* __restrict__ job_pk, uint8_t* __restrict__ out_pk96,
                                                           uint8_t* __restrict__ out_sig192,
                                                           uint8_t* __restrict__ job_bad);
+// randomized same-message aggregation (k_smrand.hip): sum s_i pk_i / sum s_i sig_i per job
+__global__ void __launch_bounds__(TPB, LB_W_SCALAR) k_sm_rand_pk(uint32_t n_jobs, const uint32_t* __restrict__ job_off,
+                                                                 PkSource pks, const uint8_t* __restrict__ seed,
+                                                                 g1j* __restrict__ out_pk,
+                                                                 uint8_t* __restrict__ pk_status,
+                                                                 uint8_t* __restrict__ out_pk96);
+__global__ void __launch_bounds__(TPB, LB_W_SSIG) k_sm_rand_sig(uint32_t n_jobs, const uint32_t* __restrict__ job_off,
+                                                                const uint8_t* __restrict__ seed,
+                                                                const g2j* __restrict__ sig,
+                                                                const uint8_t* __restrict__ sig_status,
+                                                                uint8_t* __restrict__ out_sig192,
+                                                                uint8_t* __restrict__ job_bad);
 __global__ void __launch_bounds__(TPB) k_signing_root_att(uint32_t n, const uint8_t* __restrict__ data,
                                                           const uint8_t* __restrict__ domains, uint32_t dstride,
                                                           uint8_t* __restrict__ out);

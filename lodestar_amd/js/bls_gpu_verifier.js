@@ -465,6 +465,15 @@ function hrNowNs() {
   return s * 1e9 + ns;
 }
 
+/** The addon Context options of a verifier's options: capacity (the library's calls in flight
+ * per GPU, lb_slots, unless given) and the same-message aggregation mode. */
+function contextOptions(o) {
+  const c = {};
+  if (o.capacity) c.capacity = o.capacity;
+  if (o.sameMessageRandomized) c.sameMessageRandomized = true;
+  return c;
+}
+
 class BlsGpuVerifier {
   /**
    * @param {object} o
@@ -478,13 +487,18 @@ class BlsGpuVerifier {
    * @param {boolean} [o.priorityLane] priority jobs and verifyOnMainThread calls go to the
    *   device's priority lane (lb_verify_requests_priority_async: its own high-priority
    *   stream beside the calls in flight) instead of waiting for a free slot (default true)
+   * @param {boolean} [o.sameMessageRandomized] same-message jobs are aggregated with per-set random
+   *   64-bit scalars (blst's aggregateWithRandomness; LB_SM_RANDOMIZED) instead of plain sums, so a
+   *   passing aggregate implies every set valid; for the contexts created here (default false:
+   *   the library's initial mode)
+   * @param {object} [o.addon] the addon module to create the contexts from (tests: a stand-in)
    */
   constructor(o = {}) {
+    this.sameMessageRandomized = Boolean(o.sameMessageRandomized);
     if (o.backends) this.backends = o.backends;
     else {
-      const addon = loadAddon();
-      // capacity: the library's calls in flight per GPU (lb_slots) unless given
-      this.backends = (o.devices || [0]).map((d) => new addon.Context(d, o.capacity ? {capacity: o.capacity} : {}));
+      const addon = o.addon || loadAddon();
+      this.backends = (o.devices || [0]).map((d) => new addon.Context(d, contextOptions(o)));
     }
     if (this.backends.length === 0) throw new Error("at least one GPU backend is required");
     this.blsVerifyAllMultiThread = Boolean(o.blsVerifyAllMultiThread);
@@ -865,7 +879,9 @@ class BlsGpuVerifier {
  * no buffering, every call goes straight to the device. */
 class BlsGpuSingleThreadVerifier {
   constructor(o = {}) {
-    this.backend = o.backend || new (loadAddon().Context)(o.device || 0);
+    // (o.sameMessageRandomized, o.addon: as BlsGpuVerifier)
+    this.sameMessageRandomized = Boolean(o.sameMessageRandomized);
+    this.backend = o.backend || new ((o.addon || loadAddon()).Context)(o.device || 0, contextOptions(o));
     this.seedSource = o.seedSource || (() => new Uint8Array(crypto.randomBytes(32)));
     this.metrics = o.metrics || new PoolMetrics();
     this.keyMap = new WeakMap();

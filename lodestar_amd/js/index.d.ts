@@ -91,6 +91,8 @@ export type VerifyResult = {
 /** One GPU: the N-API addon's Context (lodestar_amd/napi/addon.cc), or a mock. */
 export interface GpuBackend {
   capacity?: number;
+  /** the addon Context's same-message aggregation mode in force */
+  readonly sameMessageRandomized?: boolean;
   verifyRequests(batch: PackedRequests, opts?: {priority?: boolean}): Promise<VerifyResult>;
   verifyRequestsPartial?(batch: PackedRequests): Promise<{id: number; partial: Uint8Array}>;
   finish?(id: number, mergedOk: boolean): Promise<VerifyResult>;
@@ -120,6 +122,12 @@ export type BlsGpuVerifierOpts = {
   seedSource?: () => Uint8Array;
   /** priority jobs and verifyOnMainThread calls take the device's priority lane (default true) */
   priorityLane?: boolean;
+  /** same-message jobs aggregated with per-set random 64-bit scalars (LB_SM_RANDOMIZED: a passing
+   * aggregate implies every set valid) instead of plain sums; applies to the contexts created
+   * here, their latency lanes included (default false: the library's initial mode) */
+  sameMessageRandomized?: boolean;
+  /** the addon module the contexts are created from (tests: a stand-in; default loadAddon()) */
+  addon?: AddonModule;
 };
 
 /** BlsMultiThreadWorkerPool (chain/bls/multithread/index.ts) on GPUs. */
@@ -145,7 +153,15 @@ export class BlsGpuVerifier implements IBlsVerifier {
 
 /** BlsSingleThreadVerifier (chain/bls/singleThread.ts:10-89) on one GPU. */
 export class BlsGpuSingleThreadVerifier implements IBlsVerifier {
-  constructor(opts?: {backend?: GpuBackend; device?: number; seedSource?: () => Uint8Array; metrics?: PoolMetrics});
+  constructor(opts?: {
+    backend?: GpuBackend;
+    device?: number;
+    seedSource?: () => Uint8Array;
+    metrics?: PoolMetrics;
+    /** as BlsGpuVerifierOpts.sameMessageRandomized, for the context created here */
+    sameMessageRandomized?: boolean;
+    addon?: AddonModule;
+  });
   syncPubkeys(keys: (Uint8Array | PublicKeyLike)[], pkLen?: 48 | 96): Promise<number>;
   syncIndex2pubkey(index2pubkey: PublicKeyLike[]): Promise<number>;
   verifySignatureSets(sets: ISignatureSet[]): Promise<boolean>;
@@ -201,10 +217,11 @@ export function verifyPackedSharded(
   packed: PackedRequests,
   seedSource: () => Uint8Array
 ): Promise<{valid: Uint8Array; errors: Uint8Array; mergedOk: boolean}>;
-export function loadAddon(): {
-  deviceCount(): number;
-  Context: new (device: number, opts?: {capacity?: number}) => GpuBackend;
+export type AddonModule = {
+  deviceCount?(): number;
+  Context: new (device: number, opts?: {capacity?: number; sameMessageRandomized?: boolean}) => GpuBackend;
 };
+export function loadAddon(): AddonModule;
 
 export const MAX_SIGNATURE_SETS_PER_JOB: 128;
 export const MAX_BUFFERED_SIGS: 32;

@@ -1057,6 +1057,11 @@ napi_value New(napi_env env, napi_callback_info info) {
   int32_t capacity = 0;  // default: the library's calls in flight (lb_slots)
   napi_value v;
   if (argc >= 2 && has_prop(env, argv[1], "capacity", &v)) napi_get_value_int32(env, v, &capacity);
+  // sameMessageRandomized: true -> same-message jobs aggregated with per-set random scalars
+  // (LB_SM_RANDOMIZED) on every context created here; absent / false -> the library's initial
+  // mode (plain sums, or the operator's LB_SM_RANDOMIZED=1)
+  bool sm_randomized = false;
+  if (argc >= 2 && has_prop(env, argv[1], "sameMessageRandomized", &v)) napi_get_value_bool(env, v, &sm_randomized);
   lb_ctx* ctx = nullptr;
   const int rc = lb_create(device, &ctx);
   if (rc != LB_OK) {
@@ -1073,6 +1078,10 @@ napi_value New(napi_env env, napi_callback_info info) {
     const char* e = getenv("LB_PRIO_THREAD");
     if (!(e && atoi(e) == 0) && lb_create_lane(device, &c->lctx) != LB_OK) c->lctx = nullptr;  // (then: no lane)
   }
+  if (sm_randomized) {  // before any call: the main context and the latency lane's alike
+    lb_set_same_message_mode(c->ctx, LB_SM_RANDOMIZED);
+    if (c->lctx) lb_set_same_message_mode(c->lctx, LB_SM_RANDOMIZED);
+  }
   napi_value name;
   napi_create_string_utf8(env, "lodestar_bls_gpu", NAPI_AUTO_LENGTH, &name);
   napi_create_threadsafe_function(env, nullptr, nullptr, name, 0, 1, nullptr, nullptr, c, call_js, &c->tsfn);
@@ -1085,6 +1094,9 @@ napi_value New(napi_env env, napi_callback_info info) {
   napi_set_named_property(env, self, "device", dev);
   napi_create_int32(env, c->capacity, &cap);
   napi_set_named_property(env, self, "capacity", cap);
+  napi_value smr;  // the mode in force (the option, or the library's initial mode)
+  napi_get_boolean(env, lb_same_message_mode(c->ctx) == (int)LB_SM_RANDOMIZED, &smr);
+  napi_set_named_property(env, self, "sameMessageRandomized", smr);
   return self;
 }
 

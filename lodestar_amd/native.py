@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "lb_pubkeys_from_bytes", "lb_poll", "lb_set_latency_path", "lb_lp_program_run", "lb_scratch_per_queue",
     "lb_verify_requests_priority_async", "lb_partial_poll", "lb_hw_queues", "lb_last_call_streams",
     "lb_create_lane", "lb_mark_priority", "lb_last_latency_clocks",
+    "lb_set_same_message_mode", "lb_same_message_mode", "lb_same_message_aggregates",
 )
 
 LB_BATCH_DEVICE = 1
@@ -49,6 +50,11 @@ LB_GT_BYTES = 576
 LB_PK_ROW_FLAG = 0x80000000  # mixed packages: an index naming a row of the call's 96-byte pubkeys
 LB_PK_ROW48_FLAG = 0x40000000  # ... whose row holds a 48-byte compressed encoding
 LB_PK_ROW_MASK = 0x3FFFFFFF
+# same-message aggregation modes (lb_set_same_message_mode) and the DRBG index flag of the
+# randomized mode's scalars s_i = batch_scalar(seed, LB_SM_AGG_INDEX_FLAG | i)
+LB_SM_PLAIN = 0
+LB_SM_RANDOMIZED = 1
+LB_SM_AGG_INDEX_FLAG = 0x80000000
 
 
 class LodestarBlsError(RuntimeError):
@@ -170,6 +176,9 @@ def load_library() -> ctypes.CDLL:
                                                  ctypes.POINTER(_Stats)]
     lib.lb_verify_same_message_batch_async.argtypes = [vp, ctypes.POINTER(_SameMessageBatch), vp, vp,
                                                        ctypes.POINTER(ctypes.c_uint64)]
+    lib.lb_set_same_message_mode.argtypes = [vp, u32]
+    lib.lb_same_message_mode.argtypes = [vp]
+    lib.lb_same_message_aggregates.argtypes = [vp, ctypes.POINTER(_SameMessageBatch), vp, vp, vp]
     lib.lb_sk_to_pk.argtypes = [vp, u32, vp, vp]
     lib.lb_pubkey_table_append.argtypes = [vp, u32, vp, u32, ctypes.POINTER(ctypes.c_int32)]
     lib.lb_pubkeys_from_bytes.argtypes = [vp, u32, vp, u32, vp, vp]
@@ -396,6 +405,37 @@ class Device:
         out = ctypes.c_int32(0)
         self._check(self.lib.lb_gt_check(self._h, len(partials), _ptr(blob), ctypes.byref(out)), "lb_gt_check")
         return bool(out.value)
+
+    def set_same_message_mode(self, randomized: bool) -> None:
+        """lb_set_same_message_mode: the packages submitted from now on aggregate each job with
+        per-set random scalars (True) or with plain sums (False, the default); a package already
+        in flight keeps the mode it was submitted with."""
+        rc = self.lib.lb_set_same_message_mode(self._h, LB_SM_RANDOMIZED if randomized else LB_SM_PLAIN)
+        self._check(rc, "lb_set_same_message_mode")
+
+    @property
+    def same_message_mode(self) -> int:
+        """LB_SM_PLAIN or LB_SM_RANDOMIZED (lb_same_message_mode)."""
+        return int(self.lib.lb_same_message_mode(self._h))
+
+    def same_message_aggregates(self, jobs, seed: bytes, by_index: bool = False,
+                                rows=None) -> Tuple[List[bytes], List[bytes], List[bool]]:
+        """lb_same_message_aggregates: every job's aggregated set in the current mode, as it
+        enters the pipeline -- (96-byte keys, 192-byte signatures, bad flags) per job; a bad
+        job's encodings are all zero bytes."""
+        nj = len(jobs)
+        if nj == 0:
+            return [], [], []
+        b, _, _, _, keep = self._same_message_batch(jobs, seed, by_index, rows)
+        pk = np.zeros(nj * 96, np.uint8)
+        sig = np.zeros(nj * 192, np.uint8)
+        bad = np.zeros(nj, np.uint8)
+        rc = self.lib.lb_same_message_aggregates(self._h, ctypes.byref(b), _ptr(pk), _ptr(sig), _ptr(bad))
+        self._check(rc, "lb_same_message_aggregates")
+        del keep
+        pkb, sigb = pk.tobytes(), sig.tobytes()
+        return ([pkb[96 * j:96 * j + 96] for j in range(nj)], [sigb[192 * j:192 * j + 192] for j in range(nj)],
+                bad.astype(bool).tolist())
 
     def _same_message_batch(self, jobs, seed: bytes, by_index: bool, rows=None):
         """The lb_same_message_batch of a package, its output arrays and the

@@ -179,9 +179,16 @@ class DeviceBackend:
     several workers (multithread/index.ts:47,362-519) in one device."""
 
     def __init__(self, device: int = 0, seed_source: Callable[[], bytes] = lambda: os.urandom(32),
-                 capacity: Optional[int] = None, dev: Optional[object] = None):
+                 capacity: Optional[int] = None, dev: Optional[object] = None,
+                 same_message_randomized: bool = False):
         self.dev = dev if dev is not None else Device(device)  # dev: an injected stand-in (host tests)
         self.device = device
+        # same-message jobs aggregated with per-set random scalars (lb_set_same_message_mode:
+        # a passing aggregate then implies every set valid) instead of the plain sums; set
+        # before the first call, so every package of this backend is submitted in that mode
+        self.same_message_randomized = bool(same_message_randomized)
+        if self.same_message_randomized:
+            self.dev.set_same_message_mode(True)
         self.seed_source = seed_source
         # the library's calls in flight (lb_slots: one per HIP hardware queue of the process)
         self.capacity = capacity or (self.dev.slots() if hasattr(self.dev, "slots") else
@@ -413,10 +420,12 @@ class BlsGpuVerifier:
 
     def __init__(self, backends: Optional[Sequence[object]] = None, devices: Optional[Sequence[int]] = None,
                  blsVerifyAllMultiThread: bool = False, max_sets_per_dispatch: int = 65536,
-                 loop: Optional[asyncio.AbstractEventLoop] = None):
+                 loop: Optional[asyncio.AbstractEventLoop] = None, same_message_randomized: bool = False):
+        # same_message_randomized: for the backends created here; a backend passed in carries
+        # its own (DeviceBackend(..., same_message_randomized=True))
         if backends is None:
             devices = list(devices) if devices is not None else [0]
-            backends = [DeviceBackend(d) for d in devices]
+            backends = [DeviceBackend(d, same_message_randomized=same_message_randomized) for d in devices]
         self.backends = list(backends)
         if not self.backends:
             raise ValueError("at least one backend/device is required")
@@ -716,8 +725,9 @@ class BlsGpuSingleThreadVerifier:
     signatures, one verify; on failure each set alone (a malformed signature ->
     false).  Metrics: blsSingleThread.* and the main-thread timer."""
 
-    def __init__(self, backend: Optional[object] = None, device: int = 0):
-        self.backend = backend if backend is not None else DeviceBackend(device)
+    def __init__(self, backend: Optional[object] = None, device: int = 0, same_message_randomized: bool = False):
+        self.backend = backend if backend is not None else DeviceBackend(
+            device, same_message_randomized=same_message_randomized)
         self.pool_metrics = M.BlsPoolMetrics()
 
     async def verify_signature_sets(self, sets: List[SignatureSet],
