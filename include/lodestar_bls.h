@@ -385,6 +385,51 @@ int lb_verify_same_message_batch(lb_ctx* ctx, const lb_same_message_batch* batch
  * (BN/chain/bls/multithread/index.ts:362-519). */
 int lb_verify_same_message_batch_async(lb_ctx* ctx, const lb_same_message_batch* batch, uint8_t* out_valid,
                                        uint8_t* out_job_fast, uint64_t* out_ticket);
+/*
+ * The same verification, returning each job's aggregate signature as well: what the gossip
+ * handler's attestationPool.add does next for every valid attestation on the main thread
+ * (signatureFromBytesNoCheck + bls.Signature.aggregate([aggregate.signature, sig]),
+ * BN/chain/opPools/attestationPool.ts:182-212; also syncCommitteeMessagePool.ts:139,
+ * syncContributionAndProofPool.ts:185, aggregatedAttestationPool.ts:386), from the decoded
+ * signatures the verification already holds in HBM.  A job is one pool entry (one
+ * AttestationData), so one insert per job replaces n decompressions and additions.
+ *   For job j take every set i of the job with final out_valid[i] == 1 and (agg_mask == NULL
+ *   or agg_mask[i] != 0; agg_mask: n_sets bytes).  out_job_sig96[96 j ..] = the compressed
+ *   encoding of the plain sum of those sets' signatures, byte for byte
+ *   Signature.aggregate(those).toBytes(); out_job_count[j] = how many were summed.  A job with
+ *   count 0 (empty, every set invalid, or every set masked out) gets the compressed infinity
+ *   encoding: 0xc0 followed by 95 zero bytes.
+ * It is the plain sum in LB_SM_PLAIN and in LB_SM_RANDOMIZED alike: the scalars s_i never reach
+ * this output.  The mask affects the aggregate and nothing else: a masked-out set (the pool's
+ * AlreadyKnown case) is still verified and still gets its verdict.  out_valid, out_job_fast and
+ * stats (batch_retries, batch_sigs_success) are those of lb_verify_same_message_batch on the
+ * same input in the same mode.  The mask is copied before the call returns.
+ * THE TRAP: in LB_SM_PLAIN a job's fast path can accept a cancelling pair of signatures
+ * (sig_0 + D, sig_1 - D: every out_valid of the job is 1).  The FULL sum of such a job is still a
+ * valid aggregate, but a masked subset of it -- one that keeps one of the pair -- is not.  Only
+ * LB_SM_RANDOMIZED guarantees that every subset sum of the sets reported valid is a valid
+ * aggregate of that subset; a caller that masks should run that mode.
+ * The async form writes all four outputs when the call retires (lb_wait, or its slot's reuse).
+ * The stage shows in lb_last_stage_times as sm_job_sig (plain calls do not run it).
+ */
+int lb_verify_same_message_batch_agg(lb_ctx* ctx, const lb_same_message_batch* batch, const uint8_t* agg_mask,
+                                     uint8_t* out_valid, uint8_t* out_job_fast, uint8_t* out_job_sig96,
+                                     uint32_t* out_job_count, lb_verify_stats* stats);
+int lb_verify_same_message_batch_agg_async(lb_ctx* ctx, const lb_same_message_batch* batch, const uint8_t* agg_mask,
+                                           uint8_t* out_valid, uint8_t* out_job_fast, uint8_t* out_job_sig96,
+                                           uint32_t* out_job_count, uint64_t* out_ticket);
+/* Signature.aggregate for many groups in one call, without a verification (a pool that
+ * aggregates what it already trusts).  Group g = signatures [group_offsets[g],
+ * group_offsets[g+1]) of the call (sig_offsets: byte offsets, group_offsets[n_groups] + 1 of
+ * them); out96[96 g ..] = the compressed sum.  out_bad_index[g] = the call-wide index of the
+ * group's first signature that fails to load -- Signature.fromBytes(validate=true), or with
+ * LB_AGG_NO_CHECK signatureFromBytesNoCheck (decompression only, no subgroup check) -- else
+ * -1; a bad group's out96 is 96 zero bytes.  An empty group -> LB_ERR_INVALID_ARGUMENT
+ * (EMPTY_AGGREGATE_ARRAY, as lb_aggregate_pubkeys).  Waits for calls in flight. */
+#define LB_AGG_NO_CHECK 1u
+int lb_aggregate_signature_groups(lb_ctx* ctx, uint32_t n_groups, const uint32_t* group_offsets,
+                                  const uint8_t* signatures, const uint32_t* sig_offsets, uint32_t flags,
+                                  uint8_t* out96, int32_t* out_bad_index);
 /* Stage-level entry (like lb_hash_to_g2): the decode + aggregation of a package in the
  * context's current mode, without the verification.  out_pk96: n_jobs x 96 and out_sig192:
  * n_jobs x 192, the aggregated set of each job as it would enter the pipeline;

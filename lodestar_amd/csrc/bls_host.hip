@@ -116,6 +116,16 @@ struct SmState {
   const uint8_t* d_msgs = nullptr;
   const uint8_t* d_seed = nullptr;
   size_t ws_off = 0;                 // bump offset after phase 1 (phase 2 allocates from here)
+  // lb_verify_same_message_batch_agg: the jobs' aggregate signatures (sm_job_sig, k_aggsig.hip)
+  bool agg = false;
+  uint8_t* out_job_sig96 = nullptr;  // caller: n_jobs x 96
+  uint32_t* out_job_count = nullptr; // caller: n_jobs
+  const uint8_t* h_agg = nullptr;    // pinned: 96 nj signature bytes, then (al) nj counts
+  const uint32_t* d_joff = nullptr;
+  const uint8_t* d_mask = nullptr;   // the caller's mask (or nullptr)
+  uint8_t* d_inc = nullptr;          // per-set include flags
+  uint8_t* d_agg96 = nullptr;
+  uint32_t* d_aggcnt = nullptr;
   int err = 0;                       // a failed phase-2 launch: reported by this ticket's wait
   std::string err_msg;
 };
@@ -132,7 +142,8 @@ struct Slot {
   size_t ws_cap = 0;
   char* h_pin = nullptr;
   size_t pin_cap = 0;
-  static constexpr int kMaxStages = 32;
+  // (32 launches of the longest pipeline call, and room for what an _agg same-message call adds behind it)
+  static constexpr int kMaxStages = 40;
   hipEvent_t ev0[kMaxStages] = {}, ev1[kMaxStages] = {};
   const char* stage_name[kMaxStages] = {};
   int n_stages = 0;
@@ -2818,7 +2829,7 @@ struct SmFront {
   char* h = nullptr;  // the slot's pinned staging: inputs, then results
   const uint32_t* h_joff = nullptr;
   const uint8_t *d_pks = nullptr, *d_msgs = nullptr, *d_seed = nullptr, *d_rows = nullptr;
-  const uint32_t *d_areq = nullptr, *d_asig = nullptr;
+  const uint32_t *d_areq = nullptr, *d_asig = nullptr, *d_joff = nullptr;
   g2j* d_sig = nullptr;
   uint8_t *d_sst = nullptr, *d_jpkst = nullptr, *d_pk96 = nullptr, *d_sig192 = nullptr, *d_jbad = nullptr;
 };
@@ -2955,6 +2966,7 @@ int sm_front(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint32_t mod
   f.d_rows = d_rows;
   f.d_areq = d_areq;
   f.d_asig = d_asig;
+  f.d_joff = d_joff;
   f.d_sig = d_sig;
   f.d_sst = d_sst;
   f.d_jpkst = d_jpkst;
@@ -2964,16 +2976,50 @@ int sm_front(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint32_t mod
   return LB_OK;
 }
 
+// The caller's side of an _agg call: the optional mask, the two outputs.
+struct SmAggOut {
+  const uint8_t* mask;
+  uint8_t* sig96;
+  uint32_t* count;
+};
+
+// A run of jobs per wave with about one wave of sets in it (k_job_sig: a job of 64 sets or more
+// alone, up to LB_JS_JOBS small ones together).
+inline uint32_t job_sig_jobs_per_wg(uint32_t n_jobs, uint64_t n_sets) {
+  const uint64_t g = n_sets ? (uint64_t)TPB * n_jobs / n_sets : LB_JS_JOBS;
+  return (uint32_t)(g < 1 ? 1 : g > LB_JS_JOBS ? LB_JS_JOBS : g);
+}
+
+// The stage sm_job_sig: every job's included signatures summed and compressed (k_aggsig.hip),
+// copied into the call's pinned results.
+int sm_job_sig(lb_ctx* ctx, Slot& sl, SmState& m) {
+  const uint32_t jpw = job_sig_jobs_per_wg(m.nj, m.ns);
+  const uint32_t runs = (m.nj + jpw - 1) / jpw;
+  LB_STAGE("sm_job_sig", 0, k_job_sig, runs < 16384u ? runs : 16384u, TPB, m.nj, jpw, m.d_joff, m.d_sig,
+           (const uint8_t*)m.d_inc, m.d_agg96, m.d_aggcnt);
+  uint8_t* h = const_cast<uint8_t*>(m.h_agg);
+  LB_HIP(hipMemcpyAsync(h, m.d_agg96, (size_t)m.nj * 96, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_HIP(hipMemcpyAsync(h + al256((size_t)m.nj * 96), m.d_aggcnt, (size_t)m.nj * 4, hipMemcpyDeviceToHost,
+                        sl.st[0]));
+  return LB_OK;
+}
+
 // Phase 1 on slot `sl` (already retired by the caller); the call stays busy
 // until finish_slot, which runs sm_complete.
-int sm_submit(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint8_t* out_valid, uint8_t* out_job_fast) {
+int sm_submit(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint8_t* out_valid, uint8_t* out_job_fast,
+              const SmAggOut* agg = nullptr) {
   const uint32_t nj = b->n_jobs, ns = b->n_sets;
   const uint32_t mode = ctx->sm_mode;  // read once: the call keeps it whatever the context does later
   const size_t ns1 = ns ? ns : 1;
   const size_t retry_bytes = 2 * al256(4 * ns1) + 2 * al256(ns1);
+  // an _agg call: the mask (staged), then the jobs' signatures and counts (results), after the
+  // retry lists in the pinned area; mask, include flags and both outputs in the workspace
+  const size_t agg_pin = agg ? al256(ns1) + al256((size_t)nj * 96) + al256((size_t)nj * 4) : 0;
+  const size_t agg_ws = agg ? 2 * al256(ns1) + al256((size_t)nj * 96) + al256((size_t)nj * 4) + 4 * 256 : 0;
   Bump ws{nullptr, 0, 0};
   SmFront f;
-  LB_TRY(sm_front(ctx, sl, b, mode, retry_bytes, pipeline_ws_bytes(ctx, nj, nj) + sm_phase2_bytes(ctx, ns), ws, f));
+  LB_TRY(sm_front(ctx, sl, b, mode, retry_bytes + agg_pin,
+                  pipeline_ws_bytes(ctx, nj, nj) + sm_phase2_bytes(ctx, ns) + agg_ws, ws, f));
   const bool by_index = f.by_index;
   const size_t in_bytes = f.in_bytes, res_bytes = f.res_bytes;
   char* h = f.h;
@@ -2984,14 +3030,46 @@ int sm_submit(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint8_t* ou
   uint8_t *d_sst = f.d_sst, *d_jpkst = f.d_jpkst, *d_pk96 = f.d_pk96, *d_sig192 = f.d_sig192, *d_jbad = f.d_jbad;
   uint8_t* d_valid = ws.take<uint8_t>(nj);
   uint8_t* d_err = ws.take<uint8_t>(nj);
+  SmState& m = sl.sm;
+  m.agg = agg != nullptr;
+  char* h_res = h + in_bytes;
+  if (agg) {
+    char* h_mask = h_res + res_bytes + retry_bytes;
+    m.h_agg = (const uint8_t*)(h_mask + al256(ns1));
+    m.out_job_sig96 = agg->sig96;
+    m.out_job_count = agg->count;
+    m.d_joff = f.d_joff;
+    m.d_sig = d_sig;
+    m.nj = nj;
+    m.ns = ns;
+    uint8_t* d_mask = ws.take<uint8_t>(ns1);
+    m.d_mask = agg->mask ? d_mask : nullptr;
+    m.d_inc = ws.take<uint8_t>(ns1);
+    m.d_agg96 = ws.take<uint8_t>((size_t)nj * 96);
+    m.d_aggcnt = ws.take<uint32_t>(nj);
+    if (ws.off > ws.cap) {
+      ctx->err = "workspace overflow";
+      return LB_ERR_OUT_OF_MEMORY;
+    }
+    if (agg->mask && ns) {
+      memcpy(h_mask, agg->mask, ns);
+      LB_HIP(hipMemcpyAsync(d_mask, h_mask, ns, hipMemcpyHostToDevice, sl.st[0]));
+    }
+  }
   LB_TRY(run_pipeline(ctx, sl, nj, nj, d_areq, d_pk96, nullptr, nullptr, d_msgs, d_sig192, d_asig, d_seed, d_valid,
                       d_err, nullptr, ws));
-  char* h_res = h + in_bytes;
+  if (agg) {
+    // behind phase 1: the include decision on the device (the host's fast-path rule), then the
+    // jobs' sums -- final when no job is retried, else redone behind phase 2 (sm_advance_launch)
+    if (ns)
+      LB_STAGE("sm_job_sig", 0, k_sm_include, blocks_for(ns, 256), 256u, ns, nj, m.d_joff, (const uint8_t*)d_valid,
+               (const uint8_t*)d_err, (const uint8_t*)d_jbad, (const uint8_t*)d_jpkst, m.d_mask, m.d_inc);
+    LB_TRY(sm_job_sig(ctx, sl, m));
+  }
   LB_HIP(hipMemcpyAsync(h_res, d_valid, nj, hipMemcpyDeviceToHost, sl.st[0]));
   LB_HIP(hipMemcpyAsync(h_res + al256(nj), d_err, nj, hipMemcpyDeviceToHost, sl.st[0]));
   LB_HIP(hipMemcpyAsync(h_res + 2 * al256(nj), d_jbad, nj, hipMemcpyDeviceToHost, sl.st[0]));
   LB_HIP(hipMemcpyAsync(h_res + 3 * al256(nj), d_jpkst, nj, hipMemcpyDeviceToHost, sl.st[0]));
-  SmState& m = sl.sm;
   m.active = true;
   m.phase = 1;
   m.by_index = by_index;
@@ -3095,6 +3173,11 @@ int sm_advance_launch(lb_ctx* ctx, Slot& sl, bool block) {
                           nullptr, m.d_seed, d_rvalid, d_rerr, nullptr, ws, nullptr, d_rsig, d_rst));
       LB_HIP(hipMemcpyAsync(m.h_rout, d_rvalid, nr, hipMemcpyDeviceToHost, sl.st[0]));
       LB_HIP(hipMemcpyAsync(m.h_rout + al256(ns), d_rerr, nr, hipMemcpyDeviceToHost, sl.st[0]));
+      if (m.agg) {  // behind phase 2: the retried sets that verified alone join the sums
+        LB_STAGE("sm_job_sig", 0, k_sm_include_retry, blocks_for(nr, 256), 256u, nr, (const uint32_t*)d_rset,
+                 (const uint8_t*)d_rvalid, (const uint8_t*)d_rerr, m.d_mask, m.d_inc);
+        LB_TRY(sm_job_sig(ctx, sl, m));
+      }
       LB_TRY(end_call(ctx, sl));
       m.phase = 2;
       return LB_OK;
@@ -3104,6 +3187,10 @@ int sm_advance_launch(lb_ctx* ctx, Slot& sl, bool block) {
   // sets verified by a passing aggregate (after phase 2's own merged-check stats)
   sl.h_stats[0] = m.retried_jobs;
   sl.h_stats[1] = m.fast_sets;
+  if (m.agg) {
+    memcpy(m.out_job_sig96, m.h_agg, (size_t)nj * 96);
+    memcpy(m.out_job_count, m.h_agg + al256((size_t)nj * 96), (size_t)nj * 4);
+  }
   m.active = false;
   m.phase = 0;
   return LB_OK;
@@ -3162,6 +3249,123 @@ int lb_verify_same_message_batch(lb_ctx* ctx, const lb_same_message_batch* b, ui
   const uint64_t t = sl.ticket;
   LB_TRY(finish_slot(ctx, sl));
   fill_stats(ctx, t, stats);
+  return LB_OK;
+}
+
+// The same calls with each job's aggregate signature: the verdicts, fast flags and stats of
+// lb_verify_same_message_batch[_async], plus the stage sm_job_sig on the slot's stream.
+int lb_verify_same_message_batch_agg_async(lb_ctx* ctx, const lb_same_message_batch* b, const uint8_t* agg_mask,
+                                           uint8_t* out_valid, uint8_t* out_job_fast, uint8_t* out_job_sig96,
+                                           uint32_t* out_job_count, uint64_t* out_ticket) {
+  if (!ctx || !b || !out_ticket || (b->n_sets && !out_valid) || (b->n_jobs && (!out_job_sig96 || !out_job_count)))
+    return LB_ERR_INVALID_ARGUMENT;
+  LB_TRY(sm_validate(ctx, b));
+  LB_HIP(hipSetDevice(ctx->device));
+  LB_TRY(sm_pump(ctx));
+  Slot& sl = next_async_slot(ctx);
+  LB_TRY(finish_slot(ctx, sl));
+  pick_streams(ctx, sl);
+  if (b->n_jobs == 0) {  // nothing to verify: a call that completes at once
+    LB_TRY(begin_call(ctx, sl));
+    LB_TRY(end_call_async(ctx, sl));
+    *out_ticket = sl.ticket;
+    return LB_OK;
+  }
+  borrow_idle_stream(ctx, sl);
+  const SmAggOut agg{agg_mask, out_job_sig96, out_job_count};
+  LB_TRY(sm_submit(ctx, sl, b, out_valid, out_job_fast, &agg));
+  *out_ticket = sl.ticket;
+  return LB_OK;
+}
+
+int lb_verify_same_message_batch_agg(lb_ctx* ctx, const lb_same_message_batch* b, const uint8_t* agg_mask,
+                                     uint8_t* out_valid, uint8_t* out_job_fast, uint8_t* out_job_sig96,
+                                     uint32_t* out_job_count, lb_verify_stats* stats) {
+  if (!ctx || !b || (b->n_sets && !out_valid) || (b->n_jobs && (!out_job_sig96 || !out_job_count)))
+    return LB_ERR_INVALID_ARGUMENT;
+  if (stats) *stats = lb_verify_stats{0, 0, 0.0};
+  if (b->n_jobs == 0) return LB_OK;
+  LB_TRY(sm_validate(ctx, b));
+  LB_HIP(hipSetDevice(ctx->device));
+  BorrowGuard g{ctx};
+  LB_TRY(borrow_second_stream(ctx, g));
+  Slot& sl = ctx->slots[0];
+  LB_TRY(finish_slot(ctx, sl));
+  pick_streams(ctx, sl);
+  const SmAggOut agg{agg_mask, out_job_sig96, out_job_count};
+  LB_TRY(sm_submit(ctx, sl, b, out_valid, out_job_fast, &agg));
+  const uint64_t t = sl.ticket;
+  LB_TRY(finish_slot(ctx, sl));
+  fill_stats(ctx, t, stats);
+  return LB_OK;
+}
+
+// Signature.aggregate over many groups at once (the pools' aggregation without a verification):
+// every signature decoded once (validate=true, or LB_AGG_NO_CHECK: signatureFromBytesNoCheck),
+// then k_job_sig with "loaded" as the include flag, on the idle helper slot.
+int lb_aggregate_signature_groups(lb_ctx* ctx, uint32_t n_groups, const uint32_t* group_offsets,
+                                  const uint8_t* signatures, const uint32_t* sig_offsets, uint32_t flags,
+                                  uint8_t* out96, int32_t* out_bad_index) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  if (n_groups == 0) return LB_OK;
+  if (!group_offsets || !signatures || !sig_offsets || !out96 || !out_bad_index || (flags & ~LB_AGG_NO_CHECK)) {
+    ctx->err = "lb_aggregate_signature_groups: null pointer or unknown flag";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  if (group_offsets[0] != 0) {
+    ctx->err = "group_offsets must start at 0";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  for (uint32_t g = 0; g < n_groups; g++)
+    if (group_offsets[g + 1] <= group_offsets[g]) {
+      ctx->err = group_offsets[g + 1] == group_offsets[g] ? "EMPTY_AGGREGATE_ARRAY" : "group_offsets not monotone";
+      return LB_ERR_INVALID_ARGUMENT;
+    }
+  const uint32_t n = group_offsets[n_groups];
+  if (sig_offsets[0] != 0) return LB_ERR_INVALID_ARGUMENT;
+  for (uint32_t i = 0; i < n; i++)
+    if (sig_offsets[i + 1] < sig_offsets[i]) return LB_ERR_INVALID_ARGUMENT;
+  LB_HIP(hipSetDevice(ctx->device));
+  LB_TRY(helper_slot(ctx));
+  const size_t nb = sig_offsets[n];
+  LB_TRY(ensure_ws(ctx, nb + (size_t)n * (4 + sizeof(g2j) + 2) + (size_t)n_groups * (4 + 96 + 4) + 16 * 256));
+  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
+  void *d_s, *d_o, *d_g;
+  LB_TRY(upload(ctx, ws, signatures, nb, &d_s));
+  LB_TRY(upload(ctx, ws, sig_offsets, sizeof(uint32_t) * ((size_t)n + 1), &d_o));
+  LB_TRY(upload(ctx, ws, group_offsets, sizeof(uint32_t) * ((size_t)n_groups + 1), &d_g));
+  g2j* d_sig = ws.take<g2j>(n);
+  uint8_t* d_st = ws.take<uint8_t>(n);
+  uint8_t* d_inc = ws.take<uint8_t>(n);
+  uint8_t* d_out = ws.take<uint8_t>((size_t)n_groups * 96);
+  uint32_t* d_cnt = ws.take<uint32_t>(n_groups);
+  if (ws.off > ws.cap) {
+    ctx->err = "workspace overflow";
+    return LB_ERR_OUT_OF_MEMORY;
+  }
+  if (flags & LB_AGG_NO_CHECK)
+    LB_LAUNCH(k_decode_sigs_nocheck, blocks_for(n), TPB, n, (const uint8_t*)d_s, (const uint32_t*)d_o, d_sig, d_st);
+  else
+    LB_LAUNCH(k_decode_sigs, blocks_for(n), TPB, n, (const uint8_t*)d_s, (const uint32_t*)d_o, (const uint8_t*)nullptr,
+              d_sig, d_st);
+  LB_LAUNCH(k_inc_status, blocks_for(n, 256), 256u, n, (const uint8_t*)d_st, d_inc);
+  const uint32_t jpw = job_sig_jobs_per_wg(n_groups, n);
+  const uint32_t runs = (n_groups + jpw - 1) / jpw;
+  LB_LAUNCH(k_job_sig, runs < 16384u ? runs : 16384u, TPB, n_groups, jpw, (const uint32_t*)d_g, (const g2j*)d_sig,
+            (const uint8_t*)d_inc, d_out, d_cnt);
+  std::vector<uint8_t> st(n);
+  LB_HIP(hipMemcpyAsync(st.data(), d_st, n, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipMemcpyAsync(out96, d_out, (size_t)n_groups * 96, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  for (uint32_t g = 0; g < n_groups; g++) {
+    out_bad_index[g] = -1;
+    for (uint32_t i = group_offsets[g]; i < group_offsets[g + 1]; i++)
+      if (st[i] != LB_ST_OK) {
+        out_bad_index[g] = (int32_t)i;
+        memset(out96 + (size_t)g * 96, 0, 96);
+        break;
+      }
+  }
   return LB_OK;
 }
 

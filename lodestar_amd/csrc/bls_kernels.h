@@ -245,6 +245,29 @@ __global__ void __launch_bounds__(TPB, LB_W_SSIG) k_sm_rand_sig(uint32_t n_jobs,
                                                                 const uint8_t* __restrict__ sig_status,
                                                                 uint8_t* __restrict__ out_sig192,
                                                                 uint8_t* __restrict__ job_bad);
+// per-job aggregate signatures (k_aggsig.hip): the masked plain sum of each job's decoded
+// signatures, compressed; LB_JS_JOBS = the most jobs one wave serves
+static constexpr uint32_t LB_JS_JOBS = 16;
+__global__ void __launch_bounds__(TPB, LB_W_DECODE) k_decode_sigs_nocheck(uint32_t n, const uint8_t* __restrict__ sigs,
+                                                                          const uint32_t* __restrict__ sig_off,
+                                                                          g2j* __restrict__ out_sig,
+                                                                          uint8_t* __restrict__ status);
+__global__ void __launch_bounds__(256) k_inc_status(uint32_t n, const uint8_t* __restrict__ status,
+                                                    uint8_t* __restrict__ inc);
+__global__ void __launch_bounds__(256) k_sm_include(uint32_t n_sets, uint32_t n_jobs,
+                                                    const uint32_t* __restrict__ job_off,
+                                                    const uint8_t* __restrict__ valid, const uint8_t* __restrict__ err,
+                                                    const uint8_t* __restrict__ job_bad,
+                                                    const uint8_t* __restrict__ job_pkst,
+                                                    const uint8_t* __restrict__ mask, uint8_t* __restrict__ inc);
+__global__ void __launch_bounds__(256) k_sm_include_retry(uint32_t n_retry, const uint32_t* __restrict__ rset,
+                                                          const uint8_t* __restrict__ rvalid,
+                                                          const uint8_t* __restrict__ rerr,
+                                                          const uint8_t* __restrict__ mask, uint8_t* __restrict__ inc);
+__global__ void __launch_bounds__(TPB) k_job_sig(uint32_t n_jobs, uint32_t jobs_per_wg,
+                                                 const uint32_t* __restrict__ job_off, const g2j* __restrict__ sig,
+                                                 const uint8_t* __restrict__ inc, uint8_t* __restrict__ out96,
+                                                 uint32_t* __restrict__ out_count);
 __global__ void __launch_bounds__(TPB) k_signing_root_att(uint32_t n, const uint8_t* __restrict__ data,
                                                           const uint8_t* __restrict__ domains, uint32_t dstride,
                                                           uint8_t* __restrict__ out);

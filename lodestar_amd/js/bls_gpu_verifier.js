@@ -364,6 +364,46 @@ function packSameMessage(jobs, seed, keyMap) {
   return batch;
 }
 
+/** The mask of an aggregate same-message call: one byte per set of the package, job.include
+ * (boolean[], null: every set) in job order. */
+function sameMessageMask(jobs) {
+  const mask = new Uint8Array(jobs.reduce((s, j) => s + j.sets.length, 0));
+  let at = 0;
+  for (const j of jobs) {
+    for (let i = 0; i < j.sets.length; i++) mask[at + i] = !j.include || j.include[i] ? 1 : 0;
+    at += j.sets.length;
+  }
+  return mask;
+}
+
+/** {valid, signature, count} of job n from an aggregate call's result (signature null at count 0) */
+function aggregateResult(valid, r, n) {
+  const count = r.jobCounts[n];
+  return {valid, signature: count ? Uint8Array.from(r.jobSignatures.subarray(96 * n, 96 * n + 96)) : null, count};
+}
+
+/** bls.Signature.aggregate(group).toBytes() for every group (Uint8Array[][]) in one device call
+ * (lb_aggregate_signature_groups) -> Uint8Array[] of 96 bytes each.  Throws, as Signature.aggregate /
+ * Signature.fromBytes would, on an empty group and on a signature that fails to load
+ * (o.noCheck: loaded as signatureFromBytesNoCheck does, without the subgroup check). */
+async function aggregateSignatureGroups(backend, groups, o = {}) {
+  if (groups.length === 0) return [];
+  const groupOffsets = new Uint32Array(groups.length + 1);
+  groups.forEach((g, k) => {
+    if (g.length === 0) throw new Error("EMPTY_AGGREGATE_ARRAY");
+    groupOffsets[k + 1] = groupOffsets[k] + g.length;
+  });
+  const flat = groups.flat();
+  const sigOffsets = new Uint32Array(flat.length + 1);
+  flat.forEach((s, i) => (sigOffsets[i + 1] = sigOffsets[i] + s.length));
+  const signatures = new Uint8Array(sigOffsets[flat.length]);
+  flat.forEach((s, i) => signatures.set(s, sigOffsets[i]));
+  const r = await backend.aggregateSignatureGroups({groupOffsets, signatures, sigOffsets}, {noCheck: Boolean(o.noCheck)});
+  const bad = r.badIndex.findIndex((b) => b >= 0);
+  if (bad >= 0) throw new Error(`invalid signature ${r.badIndex[bad]} (group ${bad})`);
+  return groups.map((_, k) => Uint8Array.from(r.signatures.subarray(96 * k, 96 * k + 96)));
+}
+
 /** The reference's metric names (metrics/metrics/lodestar.ts:379-510), in-process. */
 class PoolMetrics {
   constructor() {
@@ -607,6 +647,31 @@ class BlsGpuVerifier {
     return results.flat();
   }
 
+  /**
+   * verifySignatureSetsSameMessage plus what the pools do next with the valid signatures
+   * (attestationPool.add: signatureFromBytesNoCheck + Signature.aggregate per attestation,
+   * chain/opPools/attestationPool.ts:182-212): {valid, signature, count} with signature the
+   * 96-byte compressed sum of the valid sets that opts.include (boolean[], default all) keeps,
+   * null when count is 0.  An excluded set is verified all the same.  The call is ONE job
+   * whatever its size (one aggregate); queueing, buffering and priority are those of
+   * verifySignatureSetsSameMessage and it shares its device call with the package's other
+   * same-message jobs.  Plain mode can pass a cancelling pair on the fast path: run
+   * sameMessageRandomized when a subset is summed (include/lodestar_bls.h).
+   */
+  async verifyAndAggregateSameMessage(sets, message, opts = {}) {
+    if (!(message instanceof Uint8Array) || message.length !== 32) throw new TypeError("message must be 32 bytes");
+    if (opts.include && opts.include.length !== sets.length) throw new TypeError("include: one flag per set");
+    return new Promise((resolve, reject) =>
+      this.queueBlsWork({type: "sameMessage", resolve, reject, opts, sets, message, added: Date.now(), aggregate: true,
+        include: opts.include || null})
+    );
+  }
+
+  /** bls.Signature.aggregate(group).toBytes() for every group, in one device call (see aggregateSignatureGroups) */
+  async aggregateSignatureGroups(groups, o = {}) {
+    return aggregateSignatureGroups(this.backends[0], groups, o);
+  }
+
   async close() {
     if (this.buffered) {
       clearTimeout(this.buffered.timeout);
@@ -791,7 +856,10 @@ class BlsGpuVerifier {
         const batch = packSameMessage(same, this.seedSource(), this.keyMap);
         const [s0, ns0] = process.hrtime(t0);
         m.observe(M.SIG_DESERIALIZATION_MAIN_THREAD, s0 + ns0 / 1e9);
-        waits.push(backend.verifySameMessage(batch));
+        // a job that wants its aggregate signature makes the package an aggregate call; the
+        // other jobs' verdicts are the same, their aggregates are dropped
+        if (same.some((j) => j.aggregate)) waits.push(backend.verifySameMessage(batch, {aggregate: true, mask: sameMessageMask(same)}));
+        else waits.push(backend.verifySameMessage(batch));
       }
       outs = await Promise.all(waits);
     } catch (e) {
@@ -863,7 +931,7 @@ class BlsGpuVerifier {
           m.inc(M.SAME_MESSAGE_RETRY_SETS, job.sets.length);
         }
         success += 1;
-        job.resolve(verdicts);
+        job.resolve(job.aggregate ? aggregateResult(verdicts, r, n) : verdicts);
       });
       const st = workerBatchStats(same.map(() => 1), same.map((j) => Boolean(j.opts.batchable)), Array.from(r.jobFast, (f) => f === 1));
       m.inc(M.BATCH_RETRIES, st.retries);
@@ -919,6 +987,20 @@ class BlsGpuSingleThreadVerifier {
     const r = await this.backend.verifySameMessage(packSameMessage([{sets, message}], this.seedSource(), this.keyMap));
     this.observe(t0, sets.length);
     return Array.from(r.valid.subarray(0, sets.length), (v) => v === 1);
+  }
+  /** as BlsGpuVerifier.verifyAndAggregateSameMessage, straight to the device */
+  async verifyAndAggregateSameMessage(sets, message, opts = {}) {
+    if (sets.length === 0) throw new Error("EMPTY_AGGREGATE_ARRAY");
+    if (opts.include && opts.include.length !== sets.length) throw new TypeError("include: one flag per set");
+    const t0 = process.hrtime();
+    const job = {sets, message, include: opts.include || null};
+    const r = await this.backend.verifySameMessage(packSameMessage([job], this.seedSource(), this.keyMap),
+      {aggregate: true, mask: sameMessageMask([job])});
+    this.observe(t0, sets.length);
+    return aggregateResult(Array.from(r.valid.subarray(0, sets.length), (v) => v === 1), r, 0);
+  }
+  async aggregateSignatureGroups(groups, o = {}) {
+    return aggregateSignatureGroups(this.backend, groups, o);
   }
   async close() {
     if (this.backend.close) await this.backend.close();
@@ -1058,6 +1140,8 @@ module.exports = {
   packRequests,
   packRequestsAsync,
   packSameMessage,
+  sameMessageMask,
+  aggregateSignatureGroups,
   shardRequests,
   slicePacked,
   verifyRequestsSharded,

@@ -97,17 +97,29 @@ export interface GpuBackend {
   verifyRequestsPartial?(batch: PackedRequests): Promise<{id: number; partial: Uint8Array}>;
   finish?(id: number, mergedOk: boolean): Promise<VerifyResult>;
   gtCheck?(partials: Uint8Array): Promise<boolean>;
-  verifySameMessage(batch: SameMessageBatch): Promise<{
+  /** opts.aggregate: the result also carries each job's aggregate signature (96 bytes each, the
+   * compressed sum of its valid sets that opts.mask -- one byte per set -- keeps) and count */
+  verifySameMessage(batch: SameMessageBatch, opts?: {aggregate?: boolean; mask?: Uint8Array}): Promise<{
     valid: Uint8Array;
     jobFast: Uint8Array;
     retriedJobs: number;
     fastSets: number;
     deviceMs: number;
+    jobSignatures?: Uint8Array;
+    jobCounts?: Uint32Array;
   }>;
+  aggregateSignatureGroups?(
+    batch: {groupOffsets: Uint32Array; signatures: Uint8Array; sigOffsets: Uint32Array},
+    opts?: {noCheck?: boolean}
+  ): Promise<{signatures: Uint8Array; badIndex: Int32Array}>;
   syncPubkeys?(keys: Uint8Array, pkLen: number): Promise<number>;
   aggregatePubkeys?(keys: Uint8Array | Uint32Array): Promise<Uint8Array>;
   close?(): Promise<void>;
 }
+
+/** verifyAndAggregateSameMessage: the verdicts, and what attestationPool.add would have built from
+ * the valid signatures -- their 96-byte compressed sum (null when count is 0) and how many. */
+export type SameMessageAggregate = {valid: boolean[]; signature: Uint8Array | null; count: number};
 
 export type BlsGpuVerifierOpts = {
   /** GPU ordinals, one addon Context each (default [0]) */
@@ -147,6 +159,16 @@ export class BlsGpuVerifier implements IBlsVerifier {
     message: Uint8Array,
     opts?: Omit<VerifySignatureOpts, "verifyOnMainThread">
   ): Promise<boolean[]>;
+  /** One job of any size; opts.include[i] === false leaves set i out of the sum only.  In the plain
+   * mode a fast-path job may hold a cancelling pair: sum subsets under sameMessageRandomized. */
+  verifyAndAggregateSameMessage(
+    sets: {publicKey: GpuPublicKey; signature: Uint8Array}[],
+    message: Uint8Array,
+    opts?: Omit<VerifySignatureOpts, "verifyOnMainThread"> & {include?: boolean[]}
+  ): Promise<SameMessageAggregate>;
+  /** bls.Signature.aggregate(group).toBytes() per group in one device call; throws on an empty
+   * group or a signature that fails to load (noCheck: signatureFromBytesNoCheck) */
+  aggregateSignatureGroups(groups: Uint8Array[][], opts?: {noCheck?: boolean}): Promise<Uint8Array[]>;
   close(): Promise<void>;
   canAcceptWork(): boolean;
 }
@@ -169,6 +191,12 @@ export class BlsGpuSingleThreadVerifier implements IBlsVerifier {
     sets: {publicKey: GpuPublicKey; signature: Uint8Array}[],
     message: Uint8Array
   ): Promise<boolean[]>;
+  verifyAndAggregateSameMessage(
+    sets: {publicKey: GpuPublicKey; signature: Uint8Array}[],
+    message: Uint8Array,
+    opts?: {include?: boolean[]}
+  ): Promise<SameMessageAggregate>;
+  aggregateSignatureGroups(groups: Uint8Array[][], opts?: {noCheck?: boolean}): Promise<Uint8Array[]>;
   close(): Promise<void>;
   canAcceptWork(): boolean;
 }

@@ -29,6 +29,11 @@
 //     .gtCheck(Uint8Array n*576) -> Promise<boolean>
 //     .verifySameMessage({jobOffsets, pubkeys|pubkeyIndices, signatures, sigOffsets, messages, seed})
 //         -> Promise<{valid, jobFast, retriedJobs, fastSets, deviceMs}>
+//     .verifySameMessage(batch, {aggregate: true, mask?: Uint8Array(nSets)})
+//         -> the same plus {jobSignatures: Uint8Array(nJobs*96), jobCounts: Uint32Array(nJobs)}: each
+//            job's valid (and mask-kept) signatures summed, compressed (lb_verify_same_message_batch_agg_async)
+//     .aggregateSignatureGroups({groupOffsets, signatures, sigOffsets}, {noCheck?})
+//         -> Promise<{signatures: Uint8Array(nGroups*96), badIndex: Int32Array(nGroups)}>
 //     .syncPubkeys(Uint8Array keys, pkLen) -> Promise<number>          (index2pubkey mirror)
 //     .aggregatePubkeys(Uint8Array n*96 | Uint32Array indices) -> Promise<Uint8Array(96)>
 //     .close() -> Promise<void>                                      (waits for calls in flight)
@@ -161,7 +166,7 @@ void check_offsets(const std::vector<uint32_t>& off, size_t n, uint32_t last, co
 }
 
 // ---- tasks ---------------------------------------------------------------------
-enum class Kind { Verify, Partial, Finish, SameMessage, SyncPubkeys, AggPubkeys, GtCheck, Close };
+enum class Kind { Verify, Partial, Finish, SameMessage, SyncPubkeys, AggPubkeys, AggSigGroups, GtCheck, Close };
 
 struct Task {
   Kind kind = Kind::Verify;
@@ -175,6 +180,12 @@ struct Task {
   std::vector<napi_ref> refs;
   bool has_pk_off = false, by_index = false, has_batchable = false, mixed = false;
   bool prio = false;  // verifyRequests(batch, {priority: true}): the device's priority lane
+  // verifySameMessage(batch, {aggregate, mask}): the jobs' aggregate signatures as well;
+  // aggregateSignatureGroups: groups in job_off, noCheck in no_check
+  bool agg = false, has_mask = false, no_check = false;
+  std::vector<uint8_t> mask;
+  std::vector<uint32_t> job_count;
+  std::vector<int32_t> bad_index;
   uint32_t n_req = 0, n_sets = 0, n_jobs = 0, pk_len = 0, n_keys = 0;
   int merged_ok = 0;
   uint64_t partial_id = 0;
@@ -559,8 +570,15 @@ void worker_loop(Context* c) {
         t->valid.assign(t->n_sets ? t->n_sets : 1, 0);
         t->job_fast.assign(t->n_jobs ? t->n_jobs : 1, 0);
         // in flight like a verify call (the package's per-set retries run when it retires)
+        if (t->agg) {
+          t->out_bytes.assign((size_t)(t->n_jobs ? t->n_jobs : 1) * LB_SIG_COMPRESSED, 0);
+          t->job_count.assign(t->n_jobs ? t->n_jobs : 1, 0);
+        }
         const int rc =
-            lb_verify_same_message_batch_async(c->ctx, &b, t->valid.data(), t->job_fast.data(), &t->ticket);
+            t->agg ? lb_verify_same_message_batch_agg_async(c->ctx, &b, t->has_mask ? t->mask.data() : nullptr,
+                                                            t->valid.data(), t->job_fast.data(), t->out_bytes.data(),
+                                                            t->job_count.data(), &t->ticket)
+                   : lb_verify_same_message_batch_async(c->ctx, &b, t->valid.data(), t->job_fast.data(), &t->ticket);
         if (rc != LB_OK) {
           fail(t, rc, c->ctx);
           t->t_end = now_ns();
@@ -602,6 +620,16 @@ void worker_loop(Context* c) {
           t->rc = LB_ERR_INVALID_ARGUMENT;
           t->errmsg = "invalid pubkey";
         }
+        complete(c, t);
+        break;
+      }
+      case Kind::AggSigGroups: {
+        t->out_bytes.assign((size_t)t->n_jobs * LB_SIG_COMPRESSED, 0);
+        t->bad_index.assign(t->n_jobs, -1);
+        const int rc = lb_aggregate_signature_groups(c->ctx, t->n_jobs, t->job_off.data(), t->signatures.data(),
+                                                     t->sig_off.data(), t->no_check ? LB_AGG_NO_CHECK : 0u,
+                                                     t->out_bytes.data(), t->bad_index.data());
+        if (rc != LB_OK) fail(t, rc, c->ctx);
         complete(c, t);
         break;
       }
@@ -670,6 +698,16 @@ napi_value make_u8(napi_env env, const uint8_t* p, size_t n) {
   NAPI_OK(napi_create_arraybuffer(env, n, &data, &ab));
   if (n) memcpy(data, p, n);
   NAPI_OK(napi_create_typedarray(env, napi_uint8_array, n, ab, 0, &arr));
+  return arr;
+}
+
+// n 32-bit words as a Uint32Array / Int32Array
+napi_value make_words(napi_env env, napi_typedarray_type ty, const void* p, size_t n) {
+  void* data = nullptr;
+  napi_value ab, arr;
+  napi_create_arraybuffer(env, n * 4, &data, &ab);
+  if (n) memcpy(data, p, n * 4);
+  napi_create_typedarray(env, ty, n, ab, 0, &arr);
   return arr;
 }
 
@@ -753,6 +791,17 @@ void call_js(napi_env env, napi_value /*cb*/, void* context, void* data) {
         set_num(env, result, "deviceMs", t->stats.device_ms);
         set_num(env, result, "workerStartNs", (double)t->t_start);
         set_num(env, result, "workerEndNs", (double)t->t_end);
+        if (t->agg) {
+          napi_set_named_property(env, result, "jobSignatures",
+                                  make_u8(env, t->out_bytes.data(), (size_t)t->n_jobs * LB_SIG_COMPRESSED));
+          napi_set_named_property(env, result, "jobCounts", make_words(env, napi_uint32_array, t->job_count.data(), t->n_jobs));
+        }
+        break;
+      case Kind::AggSigGroups:
+        napi_create_object(env, &result);
+        napi_set_named_property(env, result, "signatures",
+                                make_u8(env, t->out_bytes.data(), (size_t)t->n_jobs * LB_SIG_COMPRESSED));
+        napi_set_named_property(env, result, "badIndex", make_words(env, napi_int32_array, t->bad_index.data(), t->n_jobs));
         break;
       case Kind::SyncPubkeys:
         napi_create_uint32(env, t->u32, &result);
@@ -901,8 +950,8 @@ napi_value GtCheck(napi_env env, napi_callback_info info) {
 }
 
 napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
+  size_t argc = 2;
+  napi_value argv[2];
   Context* c = unwrap(env, info, &argc, argv);
   Task* t = new Task();
   t->kind = Kind::SameMessage;
@@ -938,6 +987,47 @@ napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
     }
     for (auto* v : {&t->signatures, &t->messages, &t->pubkeys}) if (v->empty()) v->push_back(0);
     if (t->pk_idx.empty()) t->pk_idx.push_back(0);
+    // {aggregate: true, mask?}: the jobs' aggregate signatures as well; without it nothing changes
+    napi_valuetype oty = napi_undefined;
+    if (argc >= 2) napi_typeof(env, argv[1], &oty);
+    napi_value av;
+    if (oty == napi_object && has_prop(env, argv[1], "aggregate", &av)) napi_get_value_bool(env, av, &t->agg);
+    if (t->agg) {
+      t->has_mask = opt_typed(env, argv[1], "mask", napi_uint8_array, t->mask);
+      if (t->has_mask && t->mask.size() != t->n_sets) throw ArgError{"mask: one byte per set"};
+      if (t->mask.empty()) t->mask.push_back(0);
+    }
+  } catch (const ArgError& e) {
+    delete t;
+    return rejected(env, e.msg);
+  }
+  return submit(env, c, t);
+}
+
+napi_value AggregateSignatureGroups(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  Context* c = unwrap(env, info, &argc, argv);
+  Task* t = new Task();
+  t->kind = Kind::AggSigGroups;
+  try {
+    if (!c || argc < 1) throw ArgError{"aggregateSignatureGroups({groupOffsets, signatures, sigOffsets}, {noCheck?})"};
+    napi_value o = argv[0];
+    req_typed(env, o, "groupOffsets", napi_uint32_array, t->job_off);
+    if (t->job_off.size() < 2) throw ArgError{"EMPTY_AGGREGATE_ARRAY"};
+    t->n_jobs = (uint32_t)t->job_off.size() - 1;
+    t->n_sets = t->job_off.back();
+    check_offsets(t->job_off, t->n_jobs, UINT32_MAX, "groupOffsets");
+    for (uint32_t g = 0; g < t->n_jobs; g++)
+      if (t->job_off[g + 1] == t->job_off[g]) throw ArgError{"EMPTY_AGGREGATE_ARRAY"};
+    req_typed(env, o, "signatures", napi_uint8_array, t->signatures);
+    req_typed(env, o, "sigOffsets", napi_uint32_array, t->sig_off);
+    check_offsets(t->sig_off, t->n_sets, (uint32_t)t->signatures.size(), "sigOffsets");
+    if (t->signatures.empty()) t->signatures.push_back(0);
+    napi_valuetype oty = napi_undefined;
+    if (argc >= 2) napi_typeof(env, argv[1], &oty);
+    napi_value nv;
+    if (oty == napi_object && has_prop(env, argv[1], "noCheck", &nv)) napi_get_value_bool(env, nv, &t->no_check);
   } catch (const ArgError& e) {
     delete t;
     return rejected(env, e.msg);
@@ -1154,6 +1244,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"verifySameMessage", nullptr, VerifySameMessage, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"syncPubkeys", nullptr, SyncPubkeys, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"aggregatePubkeys", nullptr, AggregatePubkeys, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"aggregateSignatureGroups", nullptr, AggregateSignatureGroups, nullptr, nullptr, nullptr, napi_default,
+       nullptr},
       {"close", nullptr, Close, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_value cls;

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "lb_verify_requests_priority_async", "lb_partial_poll", "lb_hw_queues", "lb_last_call_streams",
     "lb_create_lane", "lb_mark_priority", "lb_last_latency_clocks",
     "lb_set_same_message_mode", "lb_same_message_mode", "lb_same_message_aggregates",
+    "lb_verify_same_message_batch_agg", "lb_verify_same_message_batch_agg_async", "lb_aggregate_signature_groups",
 )
 
 LB_BATCH_DEVICE = 1
@@ -55,6 +56,8 @@ LB_PK_ROW_MASK = 0x3FFFFFFF
 LB_SM_PLAIN = 0
 LB_SM_RANDOMIZED = 1
 LB_SM_AGG_INDEX_FLAG = 0x80000000
+LB_AGG_NO_CHECK = 1  # lb_aggregate_signature_groups: signatureFromBytesNoCheck (no subgroup check)
+G2_INFINITY_COMPRESSED = b"\xc0" + bytes(95)  # a job aggregate of zero signatures
 
 
 class LodestarBlsError(RuntimeError):
@@ -176,6 +179,11 @@ def load_library() -> ctypes.CDLL:
                                                  ctypes.POINTER(_Stats)]
     lib.lb_verify_same_message_batch_async.argtypes = [vp, ctypes.POINTER(_SameMessageBatch), vp, vp,
                                                        ctypes.POINTER(ctypes.c_uint64)]
+    lib.lb_verify_same_message_batch_agg.argtypes = [vp, ctypes.POINTER(_SameMessageBatch), vp, vp, vp, vp, vp,
+                                                     ctypes.POINTER(_Stats)]
+    lib.lb_verify_same_message_batch_agg_async.argtypes = [vp, ctypes.POINTER(_SameMessageBatch), vp, vp, vp, vp, vp,
+                                                           ctypes.POINTER(ctypes.c_uint64)]
+    lib.lb_aggregate_signature_groups.argtypes = [vp, u32, vp, vp, vp, u32, vp, vp]
     lib.lb_set_same_message_mode.argtypes = [vp, u32]
     lib.lb_same_message_mode.argtypes = [vp]
     lib.lb_same_message_aggregates.argtypes = [vp, ctypes.POINTER(_SameMessageBatch), vp, vp, vp]
@@ -259,6 +267,9 @@ class PendingSameMessage:
     fast: np.ndarray
     job_off: np.ndarray
     keep: object
+    # aggregate=True (lb_verify_same_message_batch_agg_async): the jobs' 96-byte sums and counts
+    sig96: Optional[np.ndarray] = None
+    count: Optional[np.ndarray] = None
 
 
 class Device:
@@ -474,32 +485,74 @@ class Device:
         res = [flat[bounds[j]:bounds[j + 1]] for j in range(nj)]
         return res, fast[:nj].astype(bool).tolist(), (int(st.batch_retries), int(st.batch_sigs_success))
 
+    @staticmethod
+    def _agg_arrays(nj: int, ns: int, mask):
+        """Output arrays of an aggregate=True call and its flat mask (None: every valid set).
+        mask: one flag per set, flat or one list per job."""
+        sig96 = np.zeros(max(nj, 1) * 96, np.uint8)
+        count = np.zeros(max(nj, 1), np.uint32)
+        m = None
+        if mask is not None:
+            flat = [bool(x) for row in mask for x in (row if isinstance(row, (list, tuple, np.ndarray)) else [row])]
+            if len(flat) != ns:
+                raise ValueError("mask: one flag per set")
+            m = np.array(flat + [False], dtype=np.uint8)
+        return sig96, count, m
+
+    def _same_message_agg_result(self, out, fast, job_off, nj, st, sig96, count):
+        res, fl, stats = self._same_message_result(out, fast, job_off, nj, st)
+        self.last_stats = stats
+        self.last_device_ms = float(st.device_ms)
+        raw = sig96.tobytes()
+        return res, fl, [raw[96 * j:96 * j + 96] for j in range(nj)], count[:nj].astype(int).tolist()
+
     def verify_same_message_batch(self, jobs: Sequence[Tuple[Sequence, Sequence[bytes], bytes]], seed: bytes,
-                                  by_index: bool = False,
-                                  rows=None) -> Tuple[List[List[bool]], List[bool], Tuple[int, int]]:
+                                  by_index: bool = False, rows=None, aggregate: bool = False, mask=None):
         """jobs: (pubkeys, signatures, message) per same-message job; pubkeys are
         96-byte encodings, or validator indices when by_index.  Returns per-set
         verdicts per job, the per-job fast-path flags and (retried jobs, sets
-        verified by a passing aggregate)."""
+        verified by a passing aggregate).
+        aggregate=True (lb_verify_same_message_batch_agg): returns (valid, fast, job_sigs,
+        job_counts) instead -- per job the 96-byte compressed sum of its valid sets' signatures
+        (those the optional mask keeps) and how many were summed; the stats go to
+        self.last_stats.  Without it nothing changes."""
         nj = len(jobs)
         if nj == 0:
-            return [], [], (0, 0)
+            return ([], [], [], []) if aggregate else ([], [], (0, 0))
         b, out, fast, job_off, keep = self._same_message_batch(jobs, seed, by_index, rows)
         st = _Stats()
+        if aggregate:
+            sig96, count, m = self._agg_arrays(nj, int(job_off[-1]), mask)
+            rc = self.lib.lb_verify_same_message_batch_agg(self._h, ctypes.byref(b), _ptr(m), _ptr(out), _ptr(fast),
+                                                           _ptr(sig96), _ptr(count), ctypes.byref(st))
+            self._check(rc, "lb_verify_same_message_batch_agg")
+            del keep
+            return self._same_message_agg_result(out, fast, job_off, nj, st, sig96, count)
         rc = self.lib.lb_verify_same_message_batch(self._h, ctypes.byref(b), _ptr(out), _ptr(fast), ctypes.byref(st))
         self._check(rc, "lb_verify_same_message_batch")
         del keep
         return self._same_message_result(out, fast, job_off, nj, st)
 
+    def _submit_agg(self, b, out, fast, job_off, nj, keep, mask) -> "PendingSameMessage":
+        sig96, count, m = self._agg_arrays(nj, int(job_off[-1]), mask)
+        t = ctypes.c_uint64(0)
+        rc = self.lib.lb_verify_same_message_batch_agg_async(self._h, ctypes.byref(b), _ptr(m), _ptr(out), _ptr(fast),
+                                                             _ptr(sig96), _ptr(count), ctypes.byref(t))
+        self._check(rc, "lb_verify_same_message_batch_agg_async")
+        return PendingSameMessage(int(t.value), nj, out, fast, job_off, keep, sig96, count)
+
     def verify_same_message_batch_async(self, jobs: Sequence[Tuple[Sequence, Sequence[bytes], bytes]], seed: bytes,
-                                        by_index: bool = False) -> "PendingSameMessage":
+                                        by_index: bool = False, aggregate: bool = False,
+                                        mask=None) -> "PendingSameMessage":
         """lb_verify_same_message_batch_async: enqueue the package on the next slot of
         the ring of calls in flight and return at once; wait_same_message() gives
-        what verify_same_message_batch returns."""
+        what verify_same_message_batch returns (aggregate / mask: as there)."""
         nj = len(jobs)
         b, out, fast, job_off, keep = self._same_message_batch(jobs, seed, by_index) if nj else (
             _SameMessageBatch(0, 0, None, None, None, None, None, None, None), np.zeros(1, np.uint8),
             np.zeros(1, np.uint8), np.zeros(1, np.uint32), None)
+        if aggregate:
+            return self._submit_agg(b, out, fast, job_off, nj, keep, mask)
         t = ctypes.c_uint64(0)
         rc = self.lib.lb_verify_same_message_batch_async(self._h, ctypes.byref(b), _ptr(out), _ptr(fast),
                                                          ctypes.byref(t))
@@ -510,10 +563,12 @@ class Device:
         """A package packed once (bench: the same package resubmitted without re-packing)."""
         return (len(jobs),) + self._same_message_batch(jobs, seed, by_index)
 
-    def verify_same_message_prepared_async(self, prep) -> "PendingSameMessage":
+    def verify_same_message_prepared_async(self, prep, aggregate: bool = False, mask=None) -> "PendingSameMessage":
         nj, b, _, _, job_off, keep = prep
         out = np.zeros(max(int(job_off[-1]), 1), np.uint8)
         fast = np.zeros(max(nj, 1), np.uint8)
+        if aggregate:
+            return self._submit_agg(b, out, fast, job_off, nj, keep, mask)
         t = ctypes.c_uint64(0)
         rc = self.lib.lb_verify_same_message_batch_async(self._h, ctypes.byref(b), _ptr(out), _ptr(fast),
                                                          ctypes.byref(t))
@@ -524,6 +579,8 @@ class Device:
         st = _Stats()
         self._check(self.lib.lb_wait(self._h, pc.ticket, ctypes.byref(st)), "lb_wait")
         pc.keep = None
+        if pc.sig96 is not None:  # an aggregate=True call: (valid, fast, job_sigs, job_counts)
+            return self._same_message_agg_result(pc.out, pc.fast, pc.job_off, pc.n_jobs, st, pc.sig96, pc.count)
         res = self._same_message_result(pc.out, pc.fast, pc.job_off, pc.n_jobs, st)
         return res + (float(st.device_ms),)
 
@@ -624,6 +681,28 @@ class Device:
                                               ctypes.byref(bad))
         self._check(rc, "lb_aggregate_signatures")
         return out.tobytes(), int(bad.value)
+
+    def aggregate_signature_groups(self, groups: Sequence[Sequence[bytes]],
+                                   no_check: bool = False) -> Tuple[List[bytes], List[int]]:
+        """lb_aggregate_signature_groups: Signature.aggregate(group).toBytes() for every group in
+        one call -> (96-byte compressed sums, per group the call-wide index of its first
+        signature that fails to load, else -1; such a group's sum is 96 zero bytes).
+        no_check: signatureFromBytesNoCheck (no subgroup check)."""
+        ng = len(groups)
+        if ng == 0:
+            return [], []
+        if any(len(g) == 0 for g in groups):
+            raise EmptyAggregateError("EMPTY_AGGREGATE_ARRAY")
+        goff = np.zeros(ng + 1, np.uint32)
+        goff[1:] = np.cumsum([len(g) for g in groups])
+        blob, offs = pack_blobs([s for g in groups for s in g])
+        out = np.zeros(ng * 96, np.uint8)
+        bad = np.zeros(ng, np.int32)
+        rc = self.lib.lb_aggregate_signature_groups(self._h, ng, _ptr(goff), _ptr(blob), _ptr(offs),
+                                                    LB_AGG_NO_CHECK if no_check else 0, _ptr(out), _ptr(bad))
+        self._check(rc, "lb_aggregate_signature_groups")
+        raw = out.tobytes()
+        return [raw[96 * g:96 * g + 96] for g in range(ng)], bad.astype(int).tolist()
 
     def pubkeys_from_bytes(self, pubkeys: Sequence[bytes]) -> Tuple[List[bytes], List[int]]:
         """PublicKey.fromBytes(b, affine, validate=true) on the GPU for keys of one length
@@ -834,15 +913,17 @@ class Device:
         res = (out[:, :n_out], ofl[:, :n_outflag], float(ms.value))
         return res + (st,) if stamps else res
 
-    def last_stage_times(self, raw: bool = False) -> List[Tuple[str, float]]:
-        ms = (ctypes.c_float * 32)()
-        names = (ctypes.c_char_p * 32)()
-        n = self.lib.lb_last_stage_times(self._h, ms, names, 32)
+    def last_stage_times(self, raw: bool = False, limit: int = 32) -> List[Tuple[str, float]]:
+        """limit: launches read (32: every launch of a pipeline call; up to 40 also shows what an
+        aggregate=True same-message call adds behind the longest of them, sm_job_sig)."""
+        ms = (ctypes.c_float * limit)()
+        names = (ctypes.c_char_p * limit)()
+        n = self.lib.lb_last_stage_times(self._h, ms, names, limit)
         if raw:  # one entry per launch, in launch order (tools/opcount.py pairs them with its counters)
-            return [(names[i].decode(), float(ms[i])) for i in range(min(n, 32))]
+            return [(names[i].decode(), float(ms[i])) for i in range(min(n, limit))]
         # a stage launched more than once in a call (level_wc's passes) is reported once, summed
         out: dict = {}
-        for i in range(min(n, 32)):
+        for i in range(min(n, limit)):
             nm = names[i].decode()
             out[nm] = out.get(nm, 0.0) + float(ms[i])
         return list(out.items())

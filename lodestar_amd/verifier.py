@@ -129,6 +129,10 @@ class _Job:
     sets: list
     message: Optional[bytes] = None
     added: float = field(default_factory=time.monotonic)
+    # verify_and_aggregate_same_message: the job's aggregate signature is wanted, over the valid
+    # sets that `include` (None: all) keeps
+    aggregate: bool = False
+    include: Optional[List[bool]] = None
 
     def sig_sets(self) -> int:
         """jobItemSigSets (jobItem.ts:39-46): a same-message job counts as 1."""
@@ -259,6 +263,9 @@ class DeviceBackend:
                         # per-set retries run when it retires, on its own slot
                         pc, post = self._submit_same_message(payload)
                         inflight.append((pc, fut, post, cs))
+                    elif kind == "same_message_agg":  # ... with the jobs' aggregate signatures
+                        pc, post = self._submit_same_message(payload[0], mask=payload[1], aggregate=True)
+                        inflight.append((pc, fut, post, cs))
                     else:  # synchronous library calls (same-message batch, table sync, gt check, ...)
                         fut.set_result(payload(cs))
                 except BaseException as e:  # noqa: BLE001 -- surfaced through the future
@@ -266,6 +273,14 @@ class DeviceBackend:
                 continue
             pc, fut, post, cs = inflight.popleft()
             try:
+                if isinstance(pc, PendingSameMessage) and pc.sig96 is not None:
+                    res, fast, sigs, counts = self.dev.wait_same_message(pc)
+                    cs.batch_retries, cs.batch_sigs_success = getattr(self.dev, "last_stats", (0, 0))
+                    cs.device_ms = getattr(self.dev, "last_device_ms", 0.0)
+                    cs.stage_ms = dict(self.dev.last_stage_times())
+                    cs.t_end = time.monotonic()
+                    fut.set_result((res, fast, cs, sigs, counts))
+                    continue
                 if isinstance(pc, PendingSameMessage):
                     res, fast, (retried, ok_sets), dev_ms = self.dev.wait_same_message(pc)
                     cs.batch_retries, cs.batch_sigs_success, cs.device_ms = retried, ok_sets, dev_ms
@@ -366,17 +381,27 @@ class DeviceBackend:
     def gt_check(self, partials: Sequence[bytes]) -> concurrent.futures.Future:
         return self._put("call", lambda cs: self.dev.gt_check(list(partials)), front=True)
 
-    def _submit_same_message(self, jobs):
+    def _submit_same_message(self, jobs, mask=None, aggregate: bool = False):
         by_index = all(k.index is not None for pks, _, _ in jobs for k in pks)
         dj = [([k.index for k in pks] if by_index else self._key_bytes(pks), list(sigs), bytes(msg))
               for pks, sigs, msg in jobs]
+        if aggregate:
+            return self.dev.verify_same_message_batch_async(dj, self.seed_source(), by_index=by_index, aggregate=True,
+                                                            mask=mask), None
         return self.dev.verify_same_message_batch_async(dj, self.seed_source(), by_index=by_index), None
 
     def submit_same_message(self, jobs: Sequence[Tuple[Sequence[PublicKey], Sequence[bytes], bytes]],
-                            priority: bool = False) -> concurrent.futures.Future:
+                            priority: bool = False, aggregate: bool = False,
+                            mask: Optional[Sequence[Sequence[bool]]] = None) -> concurrent.futures.Future:
         """Future of (per-job verdict lists, per-job fast flags, CallStats): all
         same-message jobs of a package in one device call, kept in flight beside
-        the other packages (lb_verify_same_message_batch_async)."""
+        the other packages (lb_verify_same_message_batch_async).
+        aggregate=True (lb_verify_same_message_batch_agg_async): the future's result grows by
+        (per-job 96-byte aggregate signatures, per-job counts) over the valid sets that mask
+        (one flag list per job, None: every set) keeps."""
+        if aggregate:
+            return self._put("same_message_agg", (list(jobs), None if mask is None else [list(m) for m in mask]),
+                             front=priority)
         return self._put("same_message", list(jobs), front=priority)
 
     def verify_requests(self, requests: List[List[SignatureSet]]) -> Tuple[List[bool], List[int]]:
@@ -388,6 +413,15 @@ class DeviceBackend:
                             message: bytes) -> List[bool]:
         res, _, _ = self.submit_same_message([(list(pubkeys), list(signatures), message)]).result()
         return res[0]
+
+    def verify_and_aggregate_same_message(self, pubkeys: Sequence[PublicKey], signatures: Sequence[bytes],
+                                          message: bytes, include: Optional[Sequence[bool]] = None
+                                          ) -> Tuple[List[bool], Optional[bytes], int]:
+        """Blocking: one job's verdicts, its aggregate signature (None when nothing was summed) and count."""
+        res, _, _, sigs, counts = self.submit_same_message(
+            [(list(pubkeys), list(signatures), message)], aggregate=True,
+            mask=None if include is None else [list(include)]).result()
+        return res[0], (sigs[0] if counts[0] else None), int(counts[0])
 
     def sync_pubkeys(self, pubkeys: Sequence[bytes]) -> int:
         """syncPubkeys (pubkeyCache.ts:56-77): append validators' keys (48-byte
@@ -508,6 +542,30 @@ class BlsGpuVerifier:
         results = await asyncio.gather(*futs)
         return [v for r in results for v in r]
 
+    async def verify_and_aggregate_same_message(self, sets: List[Tuple[PublicKey, bytes]], message: bytes,
+                                                opts: Optional[VerifySignatureOpts] = None,
+                                                include: Optional[Sequence[bool]] = None
+                                                ) -> Tuple[List[bool], Optional[bytes], int]:
+        """verify_signature_sets_same_message plus what the pools do next with the valid
+        signatures (attestationPool.add: decompress each, fold it into the entry's aggregate;
+        chain/opPools/attestationPool.ts:182-212): (verdicts, the 96-byte compressed sum of the
+        valid sets that `include` keeps -- None when that is no set --, how many were summed).
+        include[i] = False leaves set i out of the sum only (the pool's AlreadyKnown case); it is
+        verified all the same.  The call stays ONE job whatever its size (the library takes any
+        n), so it has one aggregate; queueing, buffering and priority are those of
+        verify_signature_sets_same_message, and it shares its device call with the package's
+        other same-message jobs.  In plain mode a fast-path job may hold a cancelling pair: use
+        same_message_randomized when a subset is summed (include/lodestar_bls.h)."""
+        opts = opts or VerifySignatureOpts()
+        if len(message) != 32:
+            raise ValueError("message must be 32 bytes")
+        if include is not None and len(include) != len(sets):
+            raise ValueError("include: one flag per set")
+        fut = self._get_loop().create_future()
+        self._queue(_Job(JobType.same_message, fut, opts, list(sets), message=bytes(message), aggregate=True,
+                         include=None if include is None else [bool(x) for x in include]))
+        return await fut
+
     async def close(self) -> None:
         """index.ts:244-265: abort queued jobs, then wait for the packages already
         on a GPU and release the devices (never while a call is in flight)."""
@@ -618,7 +676,13 @@ class BlsGpuVerifier:
                     waits.append(loop.run_in_executor(None, _sync_requests, backend, reqs))
             if same_idx:
                 sm = [([p for p, _ in jobs[i].sets], [s for _, s in jobs[i].sets], jobs[i].message) for i in same_idx]
-                if hasattr(backend, "submit_same_message"):
+                if any(jobs[i].aggregate for i in same_idx):
+                    # (a plain job beside it gets its verdicts as ever; its aggregate is dropped)
+                    mask = [jobs[i].include if jobs[i].include is not None else [True] * len(jobs[i].sets)
+                            for i in same_idx]
+                    waits.append(asyncio.wrap_future(backend.submit_same_message(sm, priority=prio, aggregate=True,
+                                                                                 mask=mask)))
+                elif hasattr(backend, "submit_same_message"):
                     waits.append(asyncio.wrap_future(backend.submit_same_message(sm, priority=prio)))
                 else:
                     waits.append(loop.run_in_executor(None, _sync_same_message, backend, sm))
@@ -651,10 +715,14 @@ class BlsGpuVerifier:
             pm.inc(M.BATCH_RETRIES, retries)
             pm.inc(M.BATCH_SIGS_SUCCESS, sigs_ok)
         if same_idx:
-            verdicts, fast, cs = outs[k]
+            verdicts, fast, cs = outs[k][:3]
+            job_sigs, job_counts = outs[k][3:5] if len(outs[k]) >= 5 else (None, None)
             stats.append(cs)
             for n, i in enumerate(same_idx):
                 results[i] = ("same", verdicts[n], fast[n])
+                if jobs[i].aggregate:
+                    cnt = int(job_counts[n])
+                    results[i] += ((bytes(job_sigs[n]) if cnt else None, cnt),)
             # same-message jobs are batchable requests of one set in the worker (jobItem.ts:75-86)
             retries, sigs_ok = worker_batch_stats([1] * len(same_idx), [jobs[i].opts.batchable for i in same_idx],
                                                   list(fast))
@@ -693,7 +761,7 @@ class BlsGpuVerifier:
                     self.metrics["same_message_retry_sets"] += len(job.sets)
                     pm.inc(M.SAME_MESSAGE_RETRY_JOBS)  # index.ts:566-567
                     pm.inc(M.SAME_MESSAGE_RETRY_SETS, len(job.sets))
-                job.future.set_result(verdicts)
+                job.future.set_result((verdicts,) + r[3] if job.aggregate else verdicts)
         loop.call_soon(self._run_job)
 
     def _verify_now(self, sets: List[SignatureSet]) -> bool:
@@ -755,6 +823,21 @@ class BlsGpuSingleThreadVerifier:
         out = self.backend.verify_same_message([p for p, _ in sets], [s for _, s in sets], message)
         self.pool_metrics.observe(M.MAIN_THREAD_TIME, time.monotonic() - t0)
         return list(out)
+
+    async def verify_and_aggregate_same_message(self, sets: List[Tuple[PublicKey, bytes]], message: bytes,
+                                                opts: Optional[VerifySignatureOpts] = None,
+                                                include: Optional[Sequence[bool]] = None
+                                                ) -> Tuple[List[bool], Optional[bytes], int]:
+        """As BlsGpuVerifier.verify_and_aggregate_same_message, synchronously on the caller's thread."""
+        if len(sets) == 0:
+            raise EmptyAggregateError("EMPTY_AGGREGATE_ARRAY")
+        if include is not None and len(include) != len(sets):
+            raise ValueError("include: one flag per set")
+        t0 = time.monotonic()
+        out, sig, count = self.backend.verify_and_aggregate_same_message(
+            [p for p, _ in sets], [s for _, s in sets], message, include)
+        self.pool_metrics.observe(M.MAIN_THREAD_TIME, time.monotonic() - t0)
+        return list(out), sig, int(count)
 
     async def close(self) -> None:
         close = getattr(self.backend, "close", None)
