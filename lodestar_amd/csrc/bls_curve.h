@@ -383,8 +383,10 @@ LB_DEV void jac_mul_glv(jac<F>& r, const jac<F>& p, const uint32_t* w_c, const u
     jac_set_inf(r);
     return;
   }
-  jac_mul_glv_xy(r, p.X, p.Y, w_c, w2_c, raw);
-  fmul(r.Z, r.Z, p.Z);
+  jac<F> acc;  // (r may be p: p.Z is read after the ladder)
+  jac_mul_glv_xy(acc, p.X, p.Y, w_c, w2_c, raw);
+  fmul(acc.Z, acc.Z, p.Z);
+  r = acc;
 }
 
 // [k]P for a 32-byte big-endian scalar (secret keys: SecretKey.fromBytes is BE)
