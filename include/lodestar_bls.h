@@ -505,6 +505,58 @@ int lb_signing_roots_attestation_device(lb_ctx* ctx, uint32_t n, const uint8_t* 
 int lb_signing_roots_chunks(lb_ctx* ctx, uint32_t n, uint32_t m, const uint8_t* chunks, const uint8_t* domains,
                             uint32_t domain_stride, uint8_t* out32);
 
+/* ---- blob KZG proof verification (deneb) -----------------------------------
+ * ckzg.verifyBlobKzgProofBatch(blobs, expectedKzgCommitments, proofs) of block import
+ * (BN/chain/validation/blobSidecar.ts:195-217, surface in BN/util/kzg.ts:15-29), after
+ * consensus-specs deneb polynomial-commitments.md: per blob the Fiat-Shamir challenge z
+ * (SHA-256 over the 131,152-byte transcript), y = the blob's polynomial at z (barycentric
+ * formula over the 4096 bit-reversed roots of unity), then ONE pairing check of the
+ * random linear combination over the batch (verify_kzg_proof_batch).  Blobs are 4096
+ * 32-byte big-endian field elements; commitments and proofs 48-byte compressed G1.
+ *
+ * Per-item status: what c-kzg would have THROWN on (C_KZG_BADARGS) rather than returned
+ * false for.  Any status != LB_KZG_OK makes *out_ok = 0 without a pairing.
+ *
+ * Scheduling: synchronous calls on buffers and a stream state of their own.  Like
+ * lb_aggregate_signature_groups they wait for the context's calls in flight (which retire
+ * normally: their tickets stay valid for lb_wait / lb_poll); they take no slot, issue no
+ * ticket and never touch the pubkey table.  blobToKzgCommitment / computeBlobKzgProof are
+ * not provided (they need the Lagrange G1 setup and an MSM over it). */
+#define LB_KZG_BLOB_BYTES 131072
+#define LB_KZG_MAX_BLOBS 64
+#define LB_KZG_OK 0
+#define LB_KZG_BAD_BLOB 1       /* a field element >= r */
+#define LB_KZG_BAD_COMMITMENT 2 /* not 0xc0 || 0..., and not a compressed point of G1 */
+#define LB_KZG_BAD_PROOF 3
+#define LB_KZG_BAD_SCALAR 4     /* z or y >= r */
+/* Load [tau]_2 = KZG_SETUP_G2_MONOMIAL[1] (96 bytes, compressed) and build the roots-of-unity
+ * table.  A point that fails to decode, is infinity or lies outside G2 is refused with
+ * LB_ERR_INVALID_ARGUMENT (lb_last_error says which); the previous setup stays loaded. */
+int lb_kzg_load_setup(lb_ctx* ctx, const uint8_t* g2_tau96);
+/* 1 when a setup is loaded, 0 when not (NULL context: LB_ERR_INVALID_ARGUMENT). */
+int lb_kzg_setup_loaded(const lb_ctx* ctx);
+/* verify_blob_kzg_proof_batch.  blobs: n x LB_KZG_BLOB_BYTES; *out_ok = 1 iff every status is
+ * OK and the batch check passes; out_status (n, optional); out_each (n, optional): each
+ * item's own verdict -- all 1 when the batch passes, else verify_blob_kzg_proof of every
+ * item (0 for an item with status != OK).  n == 0 -> *out_ok = 1, nothing launched;
+ * n > LB_KZG_MAX_BLOBS, or no setup loaded -> LB_ERR_INVALID_ARGUMENT. */
+int lb_kzg_verify_blob_proof_batch(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* commitments48,
+                                   const uint8_t* proofs48, int32_t* out_ok, uint8_t* out_status,
+                                   uint8_t* out_each);
+/* verify_kzg_proof_batch: the point-evaluation check with z and y given (n x 32 bytes,
+ * big-endian; a value >= r -> LB_KZG_BAD_SCALAR). */
+int lb_kzg_verify_proof_batch(lb_ctx* ctx, uint32_t n, const uint8_t* commitments48, const uint8_t* z32,
+                              const uint8_t* y32, const uint8_t* proofs48, int32_t* out_ok, uint8_t* out_status,
+                              uint8_t* out_each);
+/* Stage-level, for parity tests: z_i = compute_challenge(blob_i, commitment_i) (the 48
+ * commitment bytes are hashed as given, not decoded) and y_i = blob_i(z_i); and y_i =
+ * blob_i(z_i) for given z_i.  out_status: LB_KZG_BAD_BLOB / LB_KZG_BAD_SCALAR; the outputs
+ * of such an item are zero bytes.  Neither needs a loaded setup. */
+int lb_kzg_blob_challenges(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* commitments48,
+                           uint8_t* out_z32, uint8_t* out_y32, uint8_t* out_status);
+int lb_kzg_evaluate(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* z32, uint8_t* out_y32,
+                    uint8_t* out_status);
+
 /* ---- stage-level entry points (parity tests against the CPU oracle) ----- */
 /* hash_to_G2(msg_i) -> 192-byte uncompressed affine encoding each */
 int lb_hash_to_g2(lb_ctx* ctx, uint32_t n, const uint8_t* messages, uint8_t* out192);
@@ -547,7 +599,8 @@ int lb_sign(lb_ctx* ctx, uint32_t n, const uint8_t* sk32, const uint8_t* message
 /* ---- profiling ----------------------------------------------------------- */
 /* Per-stage device time (ms) of the last lb_verify_* call, measured with HIP
  * events on the context's stream.  Writes up to max_stages values and their
- * names; returns the number of stages. */
+ * names; returns the number of stages.  A lb_kzg_* call reports kzg_hash,
+ * kzg_eval and kzg_tail (those of them it ran). */
 int lb_last_stage_times(const lb_ctx* ctx, float* out_ms, const char** out_names, int max_stages);
 
 #ifdef __cplusplus

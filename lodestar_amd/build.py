@@ -12,13 +12,14 @@ LIB = os.path.join(HERE, "liblodestar_bls.so")
 # one translation unit per stage group, compiled in parallel and linked into one .so
 UNITS = ["k_final.hip", "k_pairing.hip", "k_aux.hip", "k_hash.hip", "k_miller.hip", "k_scalar.hip", "k_sets.hip",
          "k_smrand.hip", "k_aggsig.hip", "k_prod.hip", "k_tail.hip", "k_ssz.hip", "k_msm.hip", "k_steps.hip", "k_lp.hip",
-         "lp_blob.hip", "bls_host.hip"]
+         "k_kzg.hip", "lp_blob.hip", "bls_host.hip"]
 HEADERS = ["bls_kernels.h", "bls_inv.h", "bls_field.h", "bls_fp_ps.h", "bls_curve.h", "bls_hash.h", "bls_pairing.h",
            "bls_wc12.h", "bls_wc12_tables.h", "gen_constants.py", "gen_fp_asm.py", "gen_wc12.py"]
 # headers / generated files only some units depend on (a regenerated program blob must
 # not rebuild every kernel unit)
 UNIT_DEPS = {"k_lp.hip": ["bls_coop.h", "bls_lp.h", "bls_lp_progs.h"], "lp_blob.hip": ["lp_programs.bin"],
-             "bls_host.hip": ["bls_lp.h", "bls_lp_progs.h"]}
+             "k_kzg.hip": ["bls_fr.h", "bls_kzg.h"],
+             "bls_host.hip": ["bls_lp.h", "bls_lp_progs.h", "bls_fr.h", "bls_kzg.h"]}
 LPGEN = os.path.join(HERE, "lpgen")
 LP_BLOB = os.path.join(CSRC, "lp_programs.bin")
 SOURCES = UNITS + HEADERS + ["bls_all.hip"] + sorted({d for v in UNIT_DEPS.values() for d in v})
@@ -104,8 +105,58 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0, lib: str = 
     if verbose:
         print(" ".join(link), flush=True)
     subprocess.check_call(link)
+    check_kzg_scratch(OBJ_DIR, verbose)
     os.replace(LIB + ".tmp", LIB)
     return LIB
+
+
+def kernel_scratch(obj: str) -> dict:
+    """Kernel name -> .private_segment_fixed_size (bytes per lane) of a unit's gfx code object."""
+    import re
+    llvm = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(HIPCC))), "llvm", "bin")
+    objdump, readelf = os.path.join(llvm, "llvm-objdump"), os.path.join(llvm, "llvm-readelf")
+    if not (os.path.exists(objdump) and os.path.exists(readelf)):
+        return {}
+    before = set(os.listdir(os.path.dirname(obj)))
+    subprocess.run([objdump, "--offloading", obj], capture_output=True, check=True)  # extracts beside obj
+    out = {}
+    for f in sorted(set(os.listdir(os.path.dirname(obj))) - before):
+        path = os.path.join(os.path.dirname(obj), f)
+        try:
+            if "amdgcn" in f:
+                notes = subprocess.run([readelf, "--notes", path], capture_output=True, text=True, check=True).stdout
+                for name, size in re.findall(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", notes):
+                    out[name] = int(size)
+        finally:
+            os.remove(path)
+    return out
+
+
+def check_kzg_scratch(obj_dir: str = OBJ_DIR, verbose: bool = False) -> None:
+    """The KZG kernels must not raise the private segment ROCr reserves per hardware queue
+    (lb_scratch_per_queue): the largest .private_segment_fixed_size among them
+    stays at or below the largest among the pipeline kernels that function lists."""
+    import re
+    host = open(os.path.join(CSRC, "bls_host.hip")).read()
+    body = host[host.index("size_t scratch_per_queue("):]
+    listed = set(re.findall(r"\(const void\*\)(k_\w+)", body[:body.index("size_t lane = 0;")]))
+    ref = 0
+    for u in UNITS:
+        if u in ("k_kzg.hip", "bls_host.hip", "lp_blob.hip"):
+            continue
+        for name, size in kernel_scratch(os.path.join(obj_dir, os.path.splitext(u)[0] + ".o")).items():
+            if any("%d%s" % (len(k), k) in name for k in listed if not k.startswith("k_kzg")):
+                ref = max(ref, size)
+    kzg = kernel_scratch(os.path.join(obj_dir, "k_kzg.o"))
+    if not kzg or not ref:
+        print("check_kzg_scratch: kernel metadata not readable, skipped", flush=True)
+        return
+    worst = max(kzg, key=kzg.get)
+    if verbose:
+        print("check_kzg_scratch: %s %d B/lane <= pipeline %d B/lane" % (worst, kzg[worst], ref), flush=True)
+    if kzg[worst] > ref:
+        raise RuntimeError("%s needs %d B/lane of private segment, above the %d lb_scratch_per_queue reports"
+                           % (worst, kzg[worst], ref))
 
 
 def build_variant(name: str, extra, verbose: bool = False, blob: str = None) -> str:

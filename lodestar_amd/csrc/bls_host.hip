@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "bls_kernels.h"
+#include "bls_kzg.h"
 #include "bls_lp.h"
 #ifdef LB_LP_PROGS_HEADER  // (a variant's programs, tools/lp_rows_variant.py)
 #include LB_LP_PROGS_HEADER
@@ -221,8 +222,20 @@ struct TicketStats {
   float wall_ms = 0.f;
 };
 
+// Blob KZG verification (lb_kzg_*): the loaded setup, the roots-of-unity table and a
+// workspace of its own (LB_KZG_MAX_BLOBS blobs), apart from the slots' workspaces.
+struct KzgState {
+  bool loaded = false;
+  fr* d_roots = nullptr;     // roots[i] = omega^brp(i), Montgomery form (k_kzg_roots)
+  g2a* d_neg_tau = nullptr;  // [0]: -[tau]_2 of the loaded setup, [1]: a candidate being checked
+  char* d_ws = nullptr;
+  size_t ws_cap = 0;
+  hipEvent_t ev[4] = {};
+};
+
 struct lb_ctx {
   int device = -1;
+  KzgState kzg;
   // One single-stream slot per hardware queue HIP gives this process: GPU_MAX_HW_QUEUES
   // (HIP's default and the box's setting are 4; at most kMaxSlots) -- more streams than
   // queues share a queue and measured -20 %, profiles/ab_r01i.txt.  That many calls are
@@ -1440,7 +1453,11 @@ size_t scratch_per_queue(int device, uint32_t* out_lane_bytes) {
                            (const void*)k_level_wc,
                            (const void*)k_msm_buckets, (const void*)k_msm_bits<TPB>, (const void*)k_msm_bits<LB_MSM_BITS_TPB>,
                            (const void*)k_decode_sigs,
-                           (const void*)k_scalar_pk, (const void*)k_sm_rand_pk, (const void*)k_sm_rand_sig};
+                           (const void*)k_scalar_pk, (const void*)k_sm_rand_pk, (const void*)k_sm_rand_sig,
+                           // (the KZG kernels stay below the pipeline's largest: build.py check_kzg_scratch)
+                           (const void*)k_kzg_hash, (const void*)k_kzg_eval, (const void*)k_kzg_decode,
+                           (const void*)k_kzg_rho, (const void*)k_kzg_ladder, (const void*)k_kzg_miller,
+                           (const void*)k_kzg_final};
   size_t lane = 0;
   for (const void* k : kernels) {
     hipFuncAttributes a{};
@@ -1792,6 +1809,11 @@ int lb_destroy(lb_ctx* ctx) {
   if (ctx->d_aux) (void)hipFree(ctx->d_aux);
   if (ctx->h_aux) (void)hipHostFree(ctx->h_aux);
   if (ctx->d_lp) (void)hipFree(ctx->d_lp);
+  if (ctx->kzg.d_roots) (void)hipFree(ctx->kzg.d_roots);
+  if (ctx->kzg.d_neg_tau) (void)hipFree(ctx->kzg.d_neg_tau);
+  if (ctx->kzg.d_ws) (void)hipFree(ctx->kzg.d_ws);
+  for (hipEvent_t e : ctx->kzg.ev)
+    if (e) (void)hipEventDestroy(e);
   {
     std::lock_guard<std::mutex> g(g_q_mu);
     g_q_plain -= ctx->q_plain;
@@ -3682,6 +3704,307 @@ int lb_sign(lb_ctx* ctx, uint32_t n, const uint8_t* sk32, const uint8_t* message
   LB_HIP(hipMemcpyAsync(out96, d_out, (size_t)n * 96, hipMemcpyDeviceToHost, ctx->stream));
   LB_HIP(hipStreamSynchronize(ctx->stream));
   return LB_OK;
+}
+
+}  // extern "C"
+
+// ============================================================================
+// Blob KZG proof verification (k_kzg.hip)
+// ============================================================================
+namespace {
+
+// device buffers of one KZG call, carved from the KZG workspace
+struct KzgBufs {
+  uint8_t *blobs, *com, *proofs, *z, *y, *status, *pt_status, *skip, *scalars, *verdict;
+  g1j *P, *lad, *AB;
+  fp12* f;
+};
+
+// The roots table, the workspace and the timing events, on first use; waits for calls in flight.
+int kzg_ensure(lb_ctx* ctx, KzgBufs& b) {
+  LB_HIP(hipSetDevice(ctx->device));
+  LB_TRY(helper_slot(ctx));
+  KzgState& k = ctx->kzg;
+  constexpr size_t M = LB_KZG_MAX_BLOBS;
+  constexpr size_t kBytes = M * (LB_KZG_BLOB_BYTES + 48 + 48 + 32 + 32 + 1 + 2 + 1 + 3 * 32) + 2 * 32 + 16 +
+                            sizeof(g1j) * (2 * M + 1 + 3 * M + 1 + 2 * M) + sizeof(fp12) * 2 * M + 32 * 256;
+  if (!k.d_ws) {
+    if (hipMalloc(&k.d_ws, kBytes) != hipSuccess) {
+      k.d_ws = nullptr;
+      ctx->err = "hipMalloc KZG workspace failed";
+      return LB_ERR_OUT_OF_MEMORY;
+    }
+    k.ws_cap = kBytes;
+  }
+  if (!k.d_neg_tau && hipMalloc(&k.d_neg_tau, 2 * sizeof(g2a)) != hipSuccess) {
+    k.d_neg_tau = nullptr;
+    ctx->err = "hipMalloc KZG setup failed";
+    return LB_ERR_OUT_OF_MEMORY;
+  }
+  for (hipEvent_t& e : k.ev)
+    if (!e) LB_HIP(hipEventCreate(&e));
+  if (!k.d_roots) {
+    fr* d = nullptr;
+    if (hipMalloc(&d, sizeof(fr) * LB_KZG_N) != hipSuccess) {
+      ctx->err = "hipMalloc KZG roots failed";
+      return LB_ERR_OUT_OF_MEMORY;
+    }
+    hipLaunchKernelGGL(k_kzg_roots, dim3(LB_KZG_N / 256), dim3(256), 0, ctx->stream, d);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+      (void)hipFree(d);
+      ctx->err = "k_kzg_roots failed";
+      return LB_ERR_DEVICE;
+    }
+    k.d_roots = d;
+  }
+  Bump ws{k.d_ws, 0, k.ws_cap};
+  b.blobs = ws.take<uint8_t>(M * LB_KZG_BLOB_BYTES);
+  b.com = ws.take<uint8_t>(M * 48);
+  b.proofs = ws.take<uint8_t>(M * 48);
+  b.z = ws.take<uint8_t>(M * 32);
+  b.y = ws.take<uint8_t>(M * 32);
+  b.status = ws.take<uint8_t>(M);
+  b.pt_status = ws.take<uint8_t>(2 * M);
+  b.skip = ws.take<uint8_t>(16);
+  b.scalars = ws.take<uint8_t>((3 * M + 1) * 32);
+  b.verdict = ws.take<uint8_t>(M);
+  b.P = ws.take<g1j>(2 * M + 1);
+  b.lad = ws.take<g1j>(3 * M + 1);
+  b.AB = ws.take<g1j>(2 * M);
+  b.f = ws.take<fp12>(2 * M);
+  if (ws.off > ws.cap) {
+    ctx->err = "KZG workspace overflow";
+    return LB_ERR_OUT_OF_MEMORY;
+  }
+  return LB_OK;
+}
+
+// The pairing tail on device-resident commitments, proofs, z and y: decode, statuses and
+// scalars, ladders, sums, two Miller loops per check, final exponentiation.  Batch mode
+// leaves one verdict, each mode one per item (the points decoded by a batch pass are reused).
+int kzg_tail(lb_ctx* ctx, const KzgBufs& b, uint32_t n, uint32_t mode) {
+  const KzgState& k = ctx->kzg;
+  if (mode == LB_KZG_BATCH)
+    LB_LAUNCH(k_kzg_decode, blocks_for(2 * n + 1), TPB, n, (const uint8_t*)b.com, (const uint8_t*)b.proofs, b.P,
+              b.pt_status);
+  LB_LAUNCH(k_kzg_rho, 1u, TPB, n, mode, (const uint8_t*)b.com, (const uint8_t*)b.proofs, (const uint8_t*)b.z,
+            (const uint8_t*)b.y, (const uint8_t*)b.pt_status, b.status, b.scalars, b.skip);
+  const uint32_t jobs = mode == LB_KZG_BATCH ? 3 * n + 1 : 2 * n;
+  LB_LAUNCH(k_kzg_ladder, blocks_for(jobs), TPB, n, mode, (const g1j*)b.P, (const uint8_t*)b.scalars,
+            (const uint8_t*)b.skip, b.lad);
+  uint32_t m = 1;
+  if (mode == LB_KZG_BATCH) {
+    // A = sum rho_i pi_i, B = sum of the other 2n + 1 ladders (a skipped batch sums stale
+    // points that nothing reads: k_kzg_miller and k_kzg_final skip too)
+    LB_LAUNCH(k_jac_sum<fp>, 1u, 256u, n, (const g1j*)b.lad, b.AB);
+    LB_LAUNCH(k_jac_sum<fp>, 1u, 256u, 2 * n + 1, (const g1j*)(b.lad + n), b.AB + 1);
+  } else {
+    m = n;
+    LB_LAUNCH(k_kzg_each_sum, blocks_for(n), TPB, n, (const g1j*)b.P, (const g1j*)b.lad, b.AB);
+  }
+  LB_LAUNCH(k_kzg_miller, blocks_for(2 * m), TPB, m, (const g1j*)b.AB, (const g2a*)k.d_neg_tau,
+            mode == LB_KZG_BATCH ? (const uint8_t*)b.skip : (const uint8_t*)nullptr, b.f);
+  LB_LAUNCH(k_kzg_final, blocks_for(m), TPB, m, mode, (const fp12*)b.f, (const uint8_t*)b.status,
+            (const uint8_t*)b.skip, b.verdict);
+  return LB_OK;
+}
+
+// stage times of a KZG call: names[i] spans ev[first + i] .. ev[first + i + 1]
+int kzg_publish_times(lb_ctx* ctx, int first, int count, const char* const* names) {
+  ctx->n_stages = 0;
+  if (!ctx->stage_events) return LB_OK;
+  for (int i = 0; i < count; i++) {
+    float ms = 0.f;
+    LB_HIP(hipEventElapsedTime(&ms, ctx->kzg.ev[first + i], ctx->kzg.ev[first + i + 1]));
+    ctx->stage_ms[i] = ms;
+    ctx->stage_name[i] = names[i];
+    ctx->stage_ops[i] = 0;
+  }
+  ctx->n_stages = count;
+  return LB_OK;
+}
+
+// verdicts of a verify call once its tail is enqueued: statuses, the batch verdict and,
+// for a failed batch with out_each, every item's own check
+int kzg_finish_verify(lb_ctx* ctx, const KzgBufs& b, uint32_t n, int32_t* out_ok, uint8_t* out_status,
+                      uint8_t* out_each) {
+  uint8_t st[LB_KZG_MAX_BLOBS], v[LB_KZG_MAX_BLOBS];
+  LB_HIP(hipMemcpyAsync(st, b.status, n, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipMemcpyAsync(v, b.verdict, 1, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  bool ok = v[0] == 1;
+  for (uint32_t i = 0; i < n; i++) ok = ok && st[i] == LB_KZG_OK;
+  *out_ok = ok ? 1 : 0;
+  if (out_status) memcpy(out_status, st, n);
+  if (out_each) {
+    if (ok) {
+      memset(out_each, 1, n);
+    } else {
+      LB_TRY(kzg_tail(ctx, b, n, LB_KZG_EACH));
+      LB_HIP(hipMemcpyAsync(v, b.verdict, n, hipMemcpyDeviceToHost, ctx->stream));
+      LB_HIP(hipStreamSynchronize(ctx->stream));
+      for (uint32_t i = 0; i < n; i++) out_each[i] = (st[i] == LB_KZG_OK && v[i] == 1) ? 1 : 0;
+    }
+  }
+  return LB_OK;
+}
+
+int kzg_check_verify_args(lb_ctx* ctx, uint32_t n, bool ptrs_ok, const char* what) {
+  if (n > LB_KZG_MAX_BLOBS) {
+    ctx->err = std::string(what) + ": more than LB_KZG_MAX_BLOBS items";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  if (!ptrs_ok) {
+    ctx->err = std::string(what) + ": null pointer";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  return LB_OK;
+}
+
+#define LB_KZG_UP(dst, src, bytes) LB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream))
+
+}  // namespace
+
+extern "C" {
+
+int lb_kzg_setup_loaded(const lb_ctx* ctx) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  return ctx->kzg.loaded ? 1 : 0;
+}
+
+int lb_kzg_load_setup(lb_ctx* ctx, const uint8_t* g2_tau96) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  if (!g2_tau96) {
+    ctx->err = "lb_kzg_load_setup: null pointer";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  KzgBufs b;
+  LB_TRY(kzg_ensure(ctx, b));
+  KzgState& k = ctx->kzg;
+  // the candidate is checked into slot [1] and copied over the loaded setup only when accepted
+  LB_KZG_UP(b.com, g2_tau96, 96);
+  LB_LAUNCH(k_kzg_setup_g2, 1u, TPB, (const uint8_t*)b.com, k.d_neg_tau + 1, b.status);
+  uint8_t st = 0xff;
+  LB_HIP(hipMemcpyAsync(&st, b.status, 1, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  if (st != LB_ST_OK) {
+    ctx->err = std::string("lb_kzg_load_setup: KZG_SETUP_G2_MONOMIAL[1] ") +
+               (st == LB_ST_PK_INFINITY ? "is the point at infinity"
+                : st == LB_ST_NOT_IN_GROUP ? "is not in G2"
+                : st == LB_ST_NOT_ON_CURVE ? "is not on the curve"
+                                           : "does not decode");
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  LB_HIP(hipMemcpyAsync(k.d_neg_tau, k.d_neg_tau + 1, sizeof(g2a), hipMemcpyDeviceToDevice, ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  k.loaded = true;
+  return LB_OK;
+}
+
+int lb_kzg_blob_challenges(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* commitments48,
+                           uint8_t* out_z32, uint8_t* out_y32, uint8_t* out_status) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  if (n == 0) return LB_OK;
+  LB_TRY(kzg_check_verify_args(ctx, n, blobs && commitments48 && out_z32 && out_y32 && out_status,
+                               "lb_kzg_blob_challenges"));
+  KzgBufs b;
+  LB_TRY(kzg_ensure(ctx, b));
+  LB_KZG_UP(b.blobs, blobs, (size_t)n * LB_KZG_BLOB_BYTES);
+  LB_KZG_UP(b.com, commitments48, (size_t)n * 48);
+  LB_HIP(hipEventRecord(ctx->kzg.ev[0], ctx->stream));
+  LB_LAUNCH(k_kzg_hash, n, LB_KZG_HASH_TPB, (const uint8_t*)b.blobs, (const uint8_t*)b.com, b.z, b.status);
+  LB_HIP(hipEventRecord(ctx->kzg.ev[1], ctx->stream));
+  LB_LAUNCH(k_kzg_eval, n, LB_KZG_EVAL_TPB, (const uint8_t*)b.blobs, (const fr*)ctx->kzg.d_roots,
+            (const uint8_t*)b.z, b.y, b.status);
+  LB_HIP(hipEventRecord(ctx->kzg.ev[2], ctx->stream));
+  LB_HIP(hipMemcpyAsync(out_z32, b.z, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipMemcpyAsync(out_y32, b.y, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipMemcpyAsync(out_status, b.status, n, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  static const char* const names[] = {"kzg_hash", "kzg_eval"};
+  return kzg_publish_times(ctx, 0, 2, names);
+}
+
+int lb_kzg_evaluate(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* z32, uint8_t* out_y32,
+                    uint8_t* out_status) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  if (n == 0) return LB_OK;
+  LB_TRY(kzg_check_verify_args(ctx, n, blobs && z32 && out_y32 && out_status, "lb_kzg_evaluate"));
+  KzgBufs b;
+  LB_TRY(kzg_ensure(ctx, b));
+  LB_KZG_UP(b.blobs, blobs, (size_t)n * LB_KZG_BLOB_BYTES);
+  LB_KZG_UP(b.z, z32, (size_t)n * 32);
+  LB_HIP(hipMemsetAsync(b.status, 0, n, ctx->stream));
+  LB_HIP(hipEventRecord(ctx->kzg.ev[1], ctx->stream));
+  LB_LAUNCH(k_kzg_eval, n, LB_KZG_EVAL_TPB, (const uint8_t*)b.blobs, (const fr*)ctx->kzg.d_roots,
+            (const uint8_t*)b.z, b.y, b.status);
+  LB_HIP(hipEventRecord(ctx->kzg.ev[2], ctx->stream));
+  LB_HIP(hipMemcpyAsync(out_y32, b.y, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipMemcpyAsync(out_status, b.status, n, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  static const char* const names[] = {"kzg_eval"};
+  return kzg_publish_times(ctx, 1, 1, names);
+}
+
+int lb_kzg_verify_blob_proof_batch(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* commitments48,
+                                   const uint8_t* proofs48, int32_t* out_ok, uint8_t* out_status,
+                                   uint8_t* out_each) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  LB_TRY(kzg_check_verify_args(ctx, n, out_ok && (n == 0 || (blobs && commitments48 && proofs48)),
+                               "lb_kzg_verify_blob_proof_batch"));
+  if (!ctx->kzg.loaded) {
+    ctx->err = "lb_kzg_verify_blob_proof_batch: no trusted setup loaded (lb_kzg_load_setup)";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  if (n == 0) {
+    *out_ok = 1;
+    return LB_OK;
+  }
+  KzgBufs b;
+  LB_TRY(kzg_ensure(ctx, b));
+  LB_KZG_UP(b.blobs, blobs, (size_t)n * LB_KZG_BLOB_BYTES);
+  LB_KZG_UP(b.com, commitments48, (size_t)n * 48);
+  LB_KZG_UP(b.proofs, proofs48, (size_t)n * 48);
+  LB_HIP(hipEventRecord(ctx->kzg.ev[0], ctx->stream));
+  LB_LAUNCH(k_kzg_hash, n, LB_KZG_HASH_TPB, (const uint8_t*)b.blobs, (const uint8_t*)b.com, b.z, b.status);
+  LB_HIP(hipEventRecord(ctx->kzg.ev[1], ctx->stream));
+  LB_LAUNCH(k_kzg_eval, n, LB_KZG_EVAL_TPB, (const uint8_t*)b.blobs, (const fr*)ctx->kzg.d_roots,
+            (const uint8_t*)b.z, b.y, b.status);
+  LB_HIP(hipEventRecord(ctx->kzg.ev[2], ctx->stream));
+  LB_TRY(kzg_tail(ctx, b, n, LB_KZG_BATCH));
+  LB_HIP(hipEventRecord(ctx->kzg.ev[3], ctx->stream));
+  LB_TRY(kzg_finish_verify(ctx, b, n, out_ok, out_status, out_each));
+  static const char* const names[] = {"kzg_hash", "kzg_eval", "kzg_tail"};
+  return kzg_publish_times(ctx, 0, 3, names);
+}
+
+int lb_kzg_verify_proof_batch(lb_ctx* ctx, uint32_t n, const uint8_t* commitments48, const uint8_t* z32,
+                              const uint8_t* y32, const uint8_t* proofs48, int32_t* out_ok, uint8_t* out_status,
+                              uint8_t* out_each) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  LB_TRY(kzg_check_verify_args(ctx, n, out_ok && (n == 0 || (commitments48 && z32 && y32 && proofs48)),
+                               "lb_kzg_verify_proof_batch"));
+  if (!ctx->kzg.loaded) {
+    ctx->err = "lb_kzg_verify_proof_batch: no trusted setup loaded (lb_kzg_load_setup)";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  if (n == 0) {
+    *out_ok = 1;
+    return LB_OK;
+  }
+  KzgBufs b;
+  LB_TRY(kzg_ensure(ctx, b));
+  LB_KZG_UP(b.com, commitments48, (size_t)n * 48);
+  LB_KZG_UP(b.proofs, proofs48, (size_t)n * 48);
+  LB_KZG_UP(b.z, z32, (size_t)n * 32);
+  LB_KZG_UP(b.y, y32, (size_t)n * 32);
+  LB_HIP(hipMemsetAsync(b.status, 0, n, ctx->stream));
+  LB_HIP(hipEventRecord(ctx->kzg.ev[2], ctx->stream));
+  LB_TRY(kzg_tail(ctx, b, n, LB_KZG_BATCH));
+  LB_HIP(hipEventRecord(ctx->kzg.ev[3], ctx->stream));
+  LB_TRY(kzg_finish_verify(ctx, b, n, out_ok, out_status, out_each));
+  static const char* const names[] = {"kzg_tail"};
+  return kzg_publish_times(ctx, 2, 1, names);
 }
 
 }  // extern "C"

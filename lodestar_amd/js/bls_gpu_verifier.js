@@ -1155,4 +1155,6 @@ module.exports = {
   PointFormat,
   LB_PK_ROW_FLAG,
   LB_PK_ROW48_FLAG,
+  // blob KZG proof verification (kzg.js): the ckzg-shaped object over an addon Context
+  createGpuKzg: require("./kzg.js").createGpuKzg,
 };

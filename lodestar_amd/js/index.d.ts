@@ -114,8 +114,35 @@ export interface GpuBackend {
   ): Promise<{signatures: Uint8Array; badIndex: Int32Array}>;
   syncPubkeys?(keys: Uint8Array, pkLen: number): Promise<number>;
   aggregatePubkeys?(keys: Uint8Array | Uint32Array): Promise<Uint8Array>;
+  /** KZG_SETUP_G2_MONOMIAL[1], 96 bytes compressed; a refused point rejects and keeps the old setup */
+  kzgLoadSetup?(g2Tau: Uint8Array): Promise<void>;
+  /** blobs n x 131072, commitments and proofs n x 48 bytes (n <= 64); status: 0 OK, 1 BAD_BLOB,
+   * 2 BAD_COMMITMENT, 3 BAD_PROOF, 4 BAD_SCALAR -- what c-kzg throws on; ok is false when any is set */
+  kzgVerifyBlobProofBatch?(
+    blobs: Uint8Array,
+    commitments: Uint8Array,
+    proofs: Uint8Array
+  ): Promise<{ok: boolean; status: Uint8Array}>;
   close?(): Promise<void>;
 }
+
+/** The verification half of `ckzg` (BN/util/kzg.ts:15-22) on the GPU (kzg.js).  Throws where c-kzg
+ * throws (lengths, a field element >= r, bytes that are no G1 point), false only for a failed
+ * pairing check.  The load and verify methods return Promises: the addon never blocks the event
+ * loop.  The two compute methods throw "not implemented: use c-kzg". */
+export interface GpuKzg {
+  freeTrustedSetup(): void;
+  loadTrustedSetup(filePath: string): Promise<void>;
+  blobToKzgCommitment(blob: Uint8Array): never;
+  computeBlobKzgProof(blob: Uint8Array, commitment: Uint8Array): never;
+  verifyBlobKzgProof(blob: Uint8Array, commitment: Uint8Array, proof: Uint8Array): Promise<boolean>;
+  verifyBlobKzgProofBatch(
+    blobs: Uint8Array[],
+    expectedKzgCommitments: Uint8Array[],
+    kzgProofs: Uint8Array[]
+  ): Promise<boolean>;
+}
+export function createGpuKzg(backend: GpuBackend): GpuKzg;
 
 /** verifyAndAggregateSameMessage: the verdicts, and what attestationPool.add would have built from
  * the valid signatures -- their 96-byte compressed sum (null when count is 0) and how many. */

@@ -34,6 +34,9 @@
 //            job's valid (and mask-kept) signatures summed, compressed (lb_verify_same_message_batch_agg_async)
 //     .aggregateSignatureGroups({groupOffsets, signatures, sigOffsets}, {noCheck?})
 //         -> Promise<{signatures: Uint8Array(nGroups*96), badIndex: Int32Array(nGroups)}>
+//     .kzgLoadSetup(Uint8Array(96)) -> Promise<void>                  (KZG_SETUP_G2_MONOMIAL[1], compressed)
+//     .kzgVerifyBlobProofBatch(blobs n*131072, commitments n*48, proofs n*48: Uint8Array)
+//         -> Promise<{ok: boolean, status: Uint8Array(n)}>             (verifyBlobKzgProofBatch; status LB_KZG_*)
 //     .syncPubkeys(Uint8Array keys, pkLen) -> Promise<number>          (index2pubkey mirror)
 //     .aggregatePubkeys(Uint8Array n*96 | Uint32Array indices) -> Promise<Uint8Array(96)>
 //     .close() -> Promise<void>                                      (waits for calls in flight)
@@ -166,7 +169,9 @@ void check_offsets(const std::vector<uint32_t>& off, size_t n, uint32_t last, co
 }
 
 // ---- tasks ---------------------------------------------------------------------
-enum class Kind { Verify, Partial, Finish, SameMessage, SyncPubkeys, AggPubkeys, AggSigGroups, GtCheck, Close };
+enum class Kind {
+  Verify, Partial, Finish, SameMessage, SyncPubkeys, AggPubkeys, AggSigGroups, GtCheck, KzgLoad, KzgVerify, Close
+};
 
 struct Task {
   Kind kind = Kind::Verify;
@@ -639,6 +644,20 @@ void worker_loop(Context* c) {
         complete(c, t);
         break;
       }
+      case Kind::KzgLoad: {
+        const int rc = lb_kzg_load_setup(c->ctx, t->pubkeys.data());
+        if (rc != LB_OK) fail(t, rc, c->ctx);
+        complete(c, t);
+        break;
+      }
+      case Kind::KzgVerify: {  // blobs in messages, commitments in pubkeys, proofs in signatures
+        t->sst.assign(t->n_keys ? t->n_keys : 1, 0);
+        const int rc = lb_kzg_verify_blob_proof_batch(c->ctx, t->n_keys, t->messages.data(), t->pubkeys.data(),
+                                                      t->signatures.data(), &t->i32, t->sst.data(), nullptr);
+        if (rc != LB_OK) fail(t, rc, c->ctx);
+        complete(c, t);
+        break;
+      }
       case Kind::Close: {
         for (Task* w : prio) {
           const int rc = lb_wait(c->ctx, w->ticket, &w->stats);
@@ -812,6 +831,17 @@ void call_js(napi_env env, napi_value /*cb*/, void* context, void* data) {
       case Kind::GtCheck:
         napi_get_boolean(env, t->i32 != 0, &result);
         break;
+      case Kind::KzgLoad:
+        napi_get_undefined(env, &result);
+        break;
+      case Kind::KzgVerify: {
+        napi_create_object(env, &result);
+        napi_value okv;
+        napi_get_boolean(env, t->i32 != 0, &okv);
+        napi_set_named_property(env, result, "ok", okv);
+        napi_set_named_property(env, result, "status", make_u8(env, t->sst.data(), t->n_keys));
+        break;
+      }
       case Kind::Close:
         napi_get_undefined(env, &result);
         break;
@@ -1090,6 +1120,50 @@ napi_value AggregatePubkeys(napi_env env, napi_callback_info info) {
   return submit(env, c, t);
 }
 
+// kzgLoadSetup(g2Tau: Uint8Array(96)): KZG_SETUP_G2_MONOMIAL[1], compressed
+napi_value KzgLoadSetup(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  Context* c = unwrap(env, info, &argc, argv);
+  Task* t = new Task();
+  t->kind = Kind::KzgLoad;
+  try {
+    if (!c || argc < 1) throw ArgError{"kzgLoadSetup(g2Tau: Uint8Array(96))"};
+    typed(env, argv[0], napi_uint8_array, "g2Tau", t->pubkeys);
+    if (t->pubkeys.size() != 96) throw ArgError{"g2Tau: 96 bytes"};
+  } catch (const ArgError& e) {
+    delete t;
+    return rejected(env, e.msg);
+  }
+  return submit(env, c, t);
+}
+
+// kzgVerifyBlobProofBatch(blobs: n x 131072, commitments: n x 48, proofs: n x 48)
+//   -> Promise<{ok: boolean, status: Uint8Array(n)}>   (status: LB_KZG_*; ok is false when any is set)
+napi_value KzgVerifyBlobProofBatch(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  Context* c = unwrap(env, info, &argc, argv);
+  Task* t = new Task();
+  t->kind = Kind::KzgVerify;
+  try {
+    if (!c || argc < 3) throw ArgError{"kzgVerifyBlobProofBatch(blobs, commitments, proofs: Uint8Array)"};
+    typed(env, argv[0], napi_uint8_array, "blobs", t->messages);
+    typed(env, argv[1], napi_uint8_array, "commitments", t->pubkeys);
+    typed(env, argv[2], napi_uint8_array, "proofs", t->signatures);
+    if (t->messages.size() % LB_KZG_BLOB_BYTES) throw ArgError{"blobs: 131072 bytes each"};
+    t->n_keys = (uint32_t)(t->messages.size() / LB_KZG_BLOB_BYTES);
+    if (t->n_keys > LB_KZG_MAX_BLOBS) throw ArgError{"blobs: more than LB_KZG_MAX_BLOBS"};
+    if (t->pubkeys.size() != (size_t)t->n_keys * 48) throw ArgError{"commitments: 48 bytes per blob"};
+    if (t->signatures.size() != (size_t)t->n_keys * 48) throw ArgError{"proofs: 48 bytes per blob"};
+    for (auto* v : {&t->messages, &t->pubkeys, &t->signatures}) if (v->empty()) v->push_back(0);
+  } catch (const ArgError& e) {
+    delete t;
+    return rejected(env, e.msg);
+  }
+  return submit(env, c, t);
+}
+
 napi_value Close(napi_env env, napi_callback_info info) {
   size_t argc = 0;
   Context* c = unwrap(env, info, &argc, nullptr);
@@ -1245,6 +1319,9 @@ napi_value Init(napi_env env, napi_value exports) {
       {"syncPubkeys", nullptr, SyncPubkeys, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"aggregatePubkeys", nullptr, AggregatePubkeys, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"aggregateSignatureGroups", nullptr, AggregateSignatureGroups, nullptr, nullptr, nullptr, napi_default,
+       nullptr},
+      {"kzgLoadSetup", nullptr, KzgLoadSetup, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"kzgVerifyBlobProofBatch", nullptr, KzgVerifyBlobProofBatch, nullptr, nullptr, nullptr, napi_default,
        nullptr},
       {"close", nullptr, Close, nullptr, nullptr, nullptr, napi_default, nullptr},
   };

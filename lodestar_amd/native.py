@@ -44,7 +44,19 @@ EXPORTED_SYMBOLS = (
     "lb_create_lane", "lb_mark_priority", "lb_last_latency_clocks",
     "lb_set_same_message_mode", "lb_same_message_mode", "lb_same_message_aggregates",
     "lb_verify_same_message_batch_agg", "lb_verify_same_message_batch_agg_async", "lb_aggregate_signature_groups",
+    "lb_kzg_load_setup", "lb_kzg_setup_loaded", "lb_kzg_verify_blob_proof_batch", "lb_kzg_verify_proof_batch",
+    "lb_kzg_blob_challenges", "lb_kzg_evaluate",
 )
+
+# blob KZG proof verification (lb_kzg_*)
+LB_KZG_BLOB_BYTES = 131072
+LB_KZG_MAX_BLOBS = 64
+LB_KZG_OK = 0
+LB_KZG_BAD_BLOB = 1
+LB_KZG_BAD_COMMITMENT = 2
+LB_KZG_BAD_PROOF = 3
+LB_KZG_BAD_SCALAR = 4
+KZG_STATUS_NAMES = {0: "OK", 1: "BAD_BLOB", 2: "BAD_COMMITMENT", 3: "BAD_PROOF", 4: "BAD_SCALAR"}
 
 LB_BATCH_DEVICE = 1
 LB_GT_BYTES = 576
@@ -184,6 +196,12 @@ def load_library() -> ctypes.CDLL:
     lib.lb_verify_same_message_batch_agg_async.argtypes = [vp, ctypes.POINTER(_SameMessageBatch), vp, vp, vp, vp, vp,
                                                            ctypes.POINTER(ctypes.c_uint64)]
     lib.lb_aggregate_signature_groups.argtypes = [vp, u32, vp, vp, vp, u32, vp, vp]
+    lib.lb_kzg_load_setup.argtypes = [vp, vp]
+    lib.lb_kzg_setup_loaded.argtypes = [vp]
+    lib.lb_kzg_verify_blob_proof_batch.argtypes = [vp, u32, vp, vp, vp, ctypes.POINTER(ctypes.c_int32), vp, vp]
+    lib.lb_kzg_verify_proof_batch.argtypes = [vp, u32, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int32), vp, vp]
+    lib.lb_kzg_blob_challenges.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+    lib.lb_kzg_evaluate.argtypes = [vp, u32, vp, vp, vp, vp]
     lib.lb_set_same_message_mode.argtypes = [vp, u32]
     lib.lb_same_message_mode.argtypes = [vp]
     lib.lb_same_message_aggregates.argtypes = [vp, ctypes.POINTER(_SameMessageBatch), vp, vp, vp]
@@ -884,6 +902,84 @@ class Device:
         out = np.zeros(max(n, 1) * 96, np.uint8)
         self._check(self.lib.lb_sign(self._h, n, _ptr(k), _ptr(m), _ptr(out)), "lb_sign")
         return [out[i * 96:(i + 1) * 96].tobytes() for i in range(n)]
+
+    # -- blob KZG proofs (lb_kzg_*) -------------------------------------------
+    @staticmethod
+    def _kzg_join(items: Sequence[bytes], size: int, what: str) -> np.ndarray:
+        for x in items:
+            if len(x) != size:
+                raise ValueError(f"{what}: expected {size} bytes, got {len(x)}")
+        return _u8(b"".join(bytes(x) for x in items)) if len(items) else np.zeros(1, np.uint8)
+
+    def kzg_load_setup(self, g2_tau96: bytes) -> None:
+        """Load KZG_SETUP_G2_MONOMIAL[1] (96 bytes compressed); a refused point keeps the old setup."""
+        a = self._kzg_join([g2_tau96], 96, "g2_tau")
+        self._check(self.lib.lb_kzg_load_setup(self._h, _ptr(a)), "lb_kzg_load_setup")
+
+    def kzg_setup_loaded(self) -> bool:
+        return int(self.lib.lb_kzg_setup_loaded(self._h)) == 1
+
+    def kzg_verify_blob_proof_batch(self, blobs: Sequence[bytes], commitments: Sequence[bytes],
+                                    proofs: Sequence[bytes], each: bool = False):
+        """-> (ok, statuses[n]) or, with each=True, (ok, statuses[n], verdicts[n])."""
+        n = len(blobs)
+        if len(commitments) != n or len(proofs) != n:
+            raise ValueError("blobs, commitments and proofs differ in length")
+        bl = self._kzg_join(blobs, LB_KZG_BLOB_BYTES, "blob")
+        c = self._kzg_join(commitments, 48, "commitment")
+        p = self._kzg_join(proofs, 48, "proof")
+        ok = ctypes.c_int32(0)
+        st = np.zeros(max(n, 1), np.uint8)
+        ea = np.zeros(max(n, 1), np.uint8) if each else None
+        self._check(self.lib.lb_kzg_verify_blob_proof_batch(self._h, n, _ptr(bl), _ptr(c), _ptr(p), ctypes.byref(ok),
+                                                            _ptr(st), _ptr(ea)), "lb_kzg_verify_blob_proof_batch")
+        res = (bool(ok.value), [int(x) for x in st[:n]])
+        return res + ([int(x) for x in ea[:n]],) if each else res
+
+    def kzg_verify_proof_batch(self, commitments: Sequence[bytes], zs: Sequence[bytes], ys: Sequence[bytes],
+                               proofs: Sequence[bytes], each: bool = False):
+        n = len(commitments)
+        if len(zs) != n or len(ys) != n or len(proofs) != n:
+            raise ValueError("commitments, z, y and proofs differ in length")
+        c = self._kzg_join(commitments, 48, "commitment")
+        z = self._kzg_join(zs, 32, "z")
+        y = self._kzg_join(ys, 32, "y")
+        p = self._kzg_join(proofs, 48, "proof")
+        ok = ctypes.c_int32(0)
+        st = np.zeros(max(n, 1), np.uint8)
+        ea = np.zeros(max(n, 1), np.uint8) if each else None
+        self._check(self.lib.lb_kzg_verify_proof_batch(self._h, n, _ptr(c), _ptr(z), _ptr(y), _ptr(p),
+                                                       ctypes.byref(ok), _ptr(st), _ptr(ea)),
+                    "lb_kzg_verify_proof_batch")
+        res = (bool(ok.value), [int(x) for x in st[:n]])
+        return res + ([int(x) for x in ea[:n]],) if each else res
+
+    def kzg_blob_challenges(self, blobs: Sequence[bytes], commitments: Sequence[bytes]):
+        """-> (z[n], y[n], statuses[n]): compute_challenge and the blob's value there, 32 bytes each."""
+        n = len(blobs)
+        if len(commitments) != n:
+            raise ValueError("blobs and commitments differ in length")
+        bl = self._kzg_join(blobs, LB_KZG_BLOB_BYTES, "blob")
+        c = self._kzg_join(commitments, 48, "commitment")
+        z = np.zeros(max(n, 1) * 32, np.uint8)
+        y = np.zeros(max(n, 1) * 32, np.uint8)
+        st = np.zeros(max(n, 1), np.uint8)
+        self._check(self.lib.lb_kzg_blob_challenges(self._h, n, _ptr(bl), _ptr(c), _ptr(z), _ptr(y), _ptr(st)),
+                    "lb_kzg_blob_challenges")
+        return ([z[32 * i:32 * i + 32].tobytes() for i in range(n)],
+                [y[32 * i:32 * i + 32].tobytes() for i in range(n)], [int(x) for x in st[:n]])
+
+    def kzg_evaluate(self, blobs: Sequence[bytes], zs: Sequence[bytes]):
+        """-> (y[n], statuses[n]): evaluate_polynomial_in_evaluation_form(blob_i, z_i)."""
+        n = len(blobs)
+        if len(zs) != n:
+            raise ValueError("blobs and z differ in length")
+        bl = self._kzg_join(blobs, LB_KZG_BLOB_BYTES, "blob")
+        z = self._kzg_join(zs, 32, "z")
+        y = np.zeros(max(n, 1) * 32, np.uint8)
+        st = np.zeros(max(n, 1), np.uint8)
+        self._check(self.lib.lb_kzg_evaluate(self._h, n, _ptr(bl), _ptr(z), _ptr(y), _ptr(st)), "lb_kzg_evaluate")
+        return [y[32 * i:32 * i + 32].tobytes() for i in range(n)], [int(x) for x in st[:n]]
 
     def set_latency_path(self, max_sets: int) -> None:
         """Calls of at most max_sets sets take the latency path (0: never)."""
