@@ -8,11 +8,17 @@
 // per lane, 1 / 2 / 4 waves per SIMD pinned by LDS, cycles per wave-product on the chip; the
 // two layouts compute the same Montgomery products (checked on the host against unsigned
 // __int128 arithmetic, and each other, for the benchmark's own inputs).
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o fp_cols_bench fp_cols_bench.hip
+// Second part (bls_fp_pow.h): operands that STAY in digit form -- a chain of resident squarings
+// and one of resident products against fp_sqr / fp_mul, one dependent chain per lane as inside
+// fp_pow_p34, and one whole resident exponentiation against the limb chain, at two waves per
+// SIMD; the two exponentiations' results are compared on the host.  Build with -DLB_POW_COLS=0
+// so that fp_pow_p34 is the limb chain:
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DLB_POW_COLS=0 -o fp_cols_bench fp_cols_bench.hip
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include "../../lodestar_amd/csrc/bls_field.h"
+#include "../../lodestar_amd/csrc/bls_fp_pow.h"
 using namespace lb;
 #define CHK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP %s @%d\n", hipGetErrorString(e), __LINE__); exit(1);} } while (0)
 
@@ -80,6 +86,42 @@ __global__ void __launch_bounds__(64, 1) k_mul(uint32_t* out, int iters) {
   out[blockIdx.x * blockDim.x + threadIdx.x] = s;
 }
 
+// the resident exponentiation out of line, as the library calls it
+__device__ __noinline__ fp_ret pow_cols_r(LB_FP_PARAMS(x)) {
+  const uint32_t a[12] = {x0, x1, x2, x3, x4, x5, x6, x7, x8, x9, x10, x11};
+  uint32_t r[12];
+  pw::pow_p34(r, a);
+  return fp_ret{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], r[10], r[11]};
+}
+// One dependent chain per lane.  V 0: fp_sqr, 1: fp_mul, 2: resident sqr, 3: resident mul,
+// 4: fp_pow_p34 (the limb chain when built with -DLB_POW_COLS=0), 5: the resident exponentiation
+template <int V>
+__global__ void __launch_bounds__(64, 2) k_chain(uint32_t* out, int iters) {
+  fp a, b;
+  seed_fp(a, threadIdx.x + 1 + 64 * blockIdx.x);
+  seed_fp(b, blockIdx.x + 7);
+  if (V == 2 || V == 3) {
+    pw::d13 x, y;
+    pw::enter(x, a.l);
+    pw::enter(y, b.l);
+#pragma unroll 1
+    for (int k = 0; k < iters; k++) {
+      if (V == 2) pw::sqr(x, x); else pw::mul(x, x, y);
+    }
+    pw::leave(a.l, x);
+  } else {
+#pragma unroll 1
+    for (int k = 0; k < iters; k++) {
+      if (V == 0) fp_sqr(a, a);
+      else if (V == 1) fp_mul(a, a, b);
+      else if (V == 4) fp_pow_p34(a, a);
+      else fp_unret(a, pow_cols_r(LB_FP_ARGS(a)));
+    }
+  }
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (int j = 0; j < 12; j++) out[12 * i + j] = a.l[j];
+}
+
 // one product of each kind for the host check
 __global__ void k_check(const uint32_t* in, uint32_t* out) {
   f30 a, b, r;
@@ -89,7 +131,7 @@ __global__ void k_check(const uint32_t* in, uint32_t* out) {
 }
 
 template <typename K>
-static void run(K kern, uint32_t* buf, int blocks, int iters, const char* name, int lds) {
+static void run(K kern, uint32_t* buf, int blocks, int iters, const char* name, int lds, int per_iter = 2) {
   hipEvent_t e0, e1; CHK(hipEventCreate(&e0)); CHK(hipEventCreate(&e1));
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, 0, buf, iters);
   CHK(hipDeviceSynchronize());
@@ -97,7 +139,7 @@ static void run(K kern, uint32_t* buf, int blocks, int iters, const char* name, 
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, 0, buf, iters);
   CHK(hipEventRecord(e1)); CHK(hipEventSynchronize(e1));
   float ms; CHK(hipEventElapsedTime(&ms, e0, e1));
-  const double ops = (double)blocks * 64 * iters * 2;
+  const double ops = (double)blocks * 64 * iters * per_iter;
   printf("%-12s blocks=%5d %8.3f ms  %.3e products/s  cycles/wave-product(chip, 2.4 GHz)=%.0f\n", name, blocks, ms,
          ops / (ms * 1e-3), 1024 * 2.4e9 / (ops / (ms * 1e-3)) * 64);
 }
@@ -169,6 +211,29 @@ int main() {
     printf("-- %d waves/SIMD\n", occ);
     run(k_mul<0>, buf, blocks, 256, "fp_mul_12x32", lds);
     run(k_mul<1>, buf, blocks, 256, "mul30_13x30", lds);
+  }
+  // resident operations (bls_fp_pow.h), one dependent chain per lane, two waves per SIMD
+  {
+    const int blocks = 2048, lds = 160 * 1024 / 4 / 2 - 1024;
+    printf("-- resident chains, 2 waves/SIMD (cycles per wave-operation)\n");
+    run(k_chain<0>, buf, blocks, 512, "fp_sqr", lds, 1);
+    run(k_chain<2>, buf, blocks, 512, "resident_sqr", lds, 1);
+    run(k_chain<1>, buf, blocks, 512, "fp_mul", lds, 1);
+    run(k_chain<3>, buf, blocks, 512, "resident_mul", lds, 1);
+    printf("-- whole exponentiation a^((p-3)/4), 2 waves/SIMD (cycles per wave-exponentiation; LB_POW_COLS=%d)\n",
+           LB_POW_COLS);
+    const size_t words = (size_t)blocks * 64 * 12;
+    uint32_t* h0 = (uint32_t*)malloc(words * 4);
+    uint32_t* h1 = (uint32_t*)malloc(words * 4);
+    run(k_chain<4>, buf, blocks, 2, "fp_pow_p34", lds, 1);
+    CHK(hipMemcpy(h0, buf, words * 4, hipMemcpyDeviceToHost));
+    run(k_chain<5>, buf, blocks, 2, "resident_pow", lds, 1);
+    CHK(hipMemcpy(h1, buf, words * 4, hipMemcpyDeviceToHost));
+    size_t diff = 0;
+    for (size_t i = 0; i < words; i++) diff += h0[i] != h1[i];
+    printf("fp_pow_p34 vs resident_pow over %zu elements: %s (%zu words differ)\n", words / 12,
+           diff ? "MISMATCH" : "identical", diff);
+    if (diff) return 1;
   }
   return 0;
 }
