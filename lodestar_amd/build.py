@@ -13,13 +13,13 @@ LIB = os.path.join(HERE, "liblodestar_bls.so")
 UNITS = ["k_final.hip", "k_pairing.hip", "k_aux.hip", "k_hash.hip", "k_miller.hip", "k_scalar.hip", "k_sets.hip",
          "k_smrand.hip", "k_aggsig.hip", "k_prod.hip", "k_tail.hip", "k_ssz.hip", "k_msm.hip", "k_steps.hip", "k_lp.hip",
          "k_kzg.hip", "lp_blob.hip", "bls_host.hip"]
-HEADERS = ["bls_kernels.h", "bls_inv.h", "bls_field.h", "bls_fp_ps.h", "bls_fp_pow.h", "bls_curve.h", "bls_hash.h",
+HEADERS = ["bls_kernels.h", "bls_limits.h", "bls_inv.h", "bls_field.h", "bls_fp_ps.h", "bls_fp_pow.h", "bls_curve.h", "bls_hash.h",
            "bls_pairing.h", "bls_wc12.h", "bls_wc12_tables.h", "gen_constants.py", "gen_fp_asm.py", "gen_wc12.py"]
 # headers / generated files only some units depend on (a regenerated program blob must
 # not rebuild every kernel unit)
 UNIT_DEPS = {"k_lp.hip": ["bls_coop.h", "bls_lp.h", "bls_lp_progs.h"], "lp_blob.hip": ["lp_programs.bin"],
              "k_kzg.hip": ["bls_fr.h", "bls_kzg.h"],
-             "bls_host.hip": ["bls_lp.h", "bls_lp_progs.h", "bls_fr.h", "bls_kzg.h"]}
+             "bls_host.hip": ["bls_lp.h", "bls_lp_progs.h", "bls_fr.h", "bls_kzg.h", "bls_plan.h"]}
 LPGEN = os.path.join(HERE, "lpgen")
 LP_BLOB = os.path.join(CSRC, "lp_programs.bin")
 SOURCES = UNITS + HEADERS + ["bls_all.hip"] + sorted({d for v in UNIT_DEPS.values() for d in v})

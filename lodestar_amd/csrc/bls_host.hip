@@ -7,20 +7,31 @@
 // Pipeline of lb_verify_requests (reference: BlsMultiThreadWorkerPool job ->
 // worker verifyManySignatureSets -> verifySignatureSetsMaybeBatch,
 // packages/beacon-node/src/chain/bls/multithread/worker.ts:30-108,
-// chain/bls/maybeBatch.ts:16-46):
-//   k_req_flags       per request : 1-set requests need core-verify checks
-//   k_decode_sigs     per set     : Signature.fromBytes(validate=true)
-//   k_pubkeys_*       per set     : PublicKey.fromBytes + PublicKey.aggregate
-//   k_hash_half/finish per message: hash_to_G2(signing root), two lanes per message
-//   k_scalar_pk       per set     : r_i pk_i (GLV, 2 x 32-bit)
-//   k_msm_*           per call    : S_all = sum r_i sig_i over the good requests, one
-//                                   bucket MSM (k_msm.hip) for the merged check; or
-//   k_scalar_sig + k_sum_tree     : r_i sig_i, S_k per request (small calls, and the
-//                                   per-request tails after a failed merged check)
-//   k_lines + k_miller_acc        : Miller(r_i pk_i, H_i) from stored lines, several
-//     (or k_miller_sets + k_prod_tree) pairs per lane, product per request
-//   k_lines_S + k_tail per request: Miller(-g1, S_k), final exponentiation, == 1,
-//                                   one wave per request (wave-cooperative Fp12)
+// chain/bls/maybeBatch.ts:16-46).  A call is planned (bls_plan.h: every decision and the
+// workspace layout, plain host arithmetic), then enqueued stage by stage (run_pipeline);
+// the default organisation of a throughput call, "steps":
+//   k_req_flags, k_rows_*  per request : 1-set requests need core-verify checks; the
+//                                        size-descending order and row offsets of the lanes
+//   k_pubkeys_*            per set     : PublicKey.fromBytes + PublicKey.aggregate
+//   k_scalar_pk            per set     : r_i pk_i (GLV, 2 x 32-bit)
+//   k_hash_half/finish     per message : hash_to_G2(signing root), two lanes per message
+//   k_lines_rows           per set     : the 68 lines of (r_i pk_i, H_i), stored
+//   k_decode_sigs          per set     : Signature.fromBytes(validate=true)
+//   k_req_status           per request : rejection codes, bad requests
+//   k_msm_*                per call    : S_all = sum r_i sig_i over the good requests, one
+//                                        bucket MSM (k_msm.hip); small calls: per-set ladders
+//                                        (k_scalar_sig + k_sum_tree), also the S_k of the tails
+//   k_step_acc             per set     : step-major lanes over the stored lines (k_steps.hip)
+//   k_level_part/_wc       per call    : the 63 level products of the merged check
+//   k_lp_mtail             per call    : merged check as a round program: S_all from the MSM's
+//                                        bit sums, Miller(-g1, S_all), Horner chain, final exp
+//   k_req_horner + k_lp_rtail per request, only after a failed merged check: F_k,
+//                                        Miller(-g1, S_k), final exponentiation, == 1
+// A lone mid-size call runs hash finish, decode and lines as round programs (k_lp_*); the
+// pairs organisation (LB_ACC=pairs: k_lines + k_miller_acc, several pairs per lane), the
+// per-set Miller loops of small calls (k_miller_sets / k_pair_wc + k_prod_tree) and the
+// one-wave tails (k_lines_S + k_tail) remain selectable; calls of at most 1,024 sets take
+// the latency path (run_lp, k_lp.hip) instead.  DESIGN.md §4.5-4.6.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -36,6 +47,7 @@
 #include "bls_kernels.h"
 #include "bls_kzg.h"
 #include "bls_lp.h"
+#include "bls_plan.h"
 #ifdef LB_LP_PROGS_HEADER  // (a variant's programs, tools/lp_rows_variant.py)
 #include LB_LP_PROGS_HEADER
 #else
@@ -269,82 +281,21 @@ struct lb_ctx {
   static constexpr int kTwoPhaseRing = 256;
   uint64_t two_phase[kTwoPhaseRing] = {};
   int two_phase_pos = 0;
-  // LB_TP_RELEASE (default 1): a two-phase call completes as if the combined check passed and
-  // frees its slot when its partial is out, instead of holding the slot through the host's
-  // combine (-5..-7 % at N = 1); a failed combined check re-runs the shard
-  // as a one-phase call.  One record per two-phase ticket (ring by ticket).
-  bool tp_release = true;  // the mode of the two-phase call being submitted
-  // LB_TP_RELEASE as configured; after a failed combined check the next tp_pause_calls two-phase
-  // calls take the legacy mode: a re-run repeats the whole shard (one wrong set per C2 call:
-  // 1.07 M sets/s released against 1.98 M legacy, bench.py adversarial_two_phase), the legacy
-  // mode runs only the per-request tails, so a stream of failing batches (invalid gossip)
-  // costs the tails alone while a clean stream keeps the release
-  bool tp_release_cfg = true;
+  // (LB_TP_RELEASE: cfg.tp_release / cfg.tp_release_cfg; one record per two-phase ticket, ring by ticket)
   uint32_t tp_pause = 0;
   uint32_t tp_pause_calls = 32;  // (LB_TP_PAUSE; 0: always release)
   bool fault_rerun = false;  // LB_FAULT_RERUN=1 (tests only): a failed combine's re-run fails to submit
   TwoPhaseRec tp[kTwoPhaseRing];
   ErrorText err;
   hipStream_t stream = nullptr;  // slot 0 stream 0 (synchronous helper calls)
-  // Miller organisation: stored lines + one wave per pair (k_lines/k_pair_wc,
-  // lowest latency) up to wave_max_sets; one pair per lane (k_miller_sets)
-  // below lines_min_sets; stored lines + multi-pair accumulation per request
-  // (k_lines/k_miller_acc, highest throughput) from there.  LB_MILLER=wave|lane|lines forces one.
-  int miller_mode = 0;  // 0 auto, 1 lane, 2 lines, 3 wave
-  // 1025: every call the latency path does not take (lp_max_sets) uses the stored lines;
-  // 1.5k-6k-set calls 25-29 -> 17-19 ms, C5 27.2 -> 21.0 ms (profiles/r06/orgs_probe_r06f.json)
-  uint32_t lines_min_sets = 1025;
-  uint32_t wave_max_sets = 1024;
-  // LB_LINES_WAVES: 1 or 2 waves/SIMD for k_lines(_rows): 2 spills (3.4 -> 4.7 ms alone) but its
-  // waves share SIMDs with other calls' in the pipeline (profiles/ab_r03/ab_r03r, ab_r03s)
-  int lines_waves = 2;
-  int lines_waves_small = 1;  // k_lines for the calls below the steps organisation
-  int acc_lpr = 64;     // LB_ACC_LPR: lanes per request in k_miller_acc (64, 32, 16)
-  int acc_split = -1;   // LB_ACC_SPLIT: 1 always / 0 never split requests in halves; -1 = lone calls only
-  // Miller accumulation of the stored lines: 1 = step-major lanes + level products +
-  // one Horner chain (k_steps.hip, default), 0 = pair-major k_miller_acc (LB_ACC=pairs)
-  int acc_steps = 1;
+  // the switches that shape a pipeline call (bls_plan.h: plan_pipeline reads nothing else)
+  PipeConfig cfg;
   // LB_DAG=0: a call never borrows a second stream (every kernel of a lone call runs
   // alone on the GPU: bench.py's per-kernel iso timings and their rocprof profile)
   bool dag = true;
-  // LB_STEP_MODE: k_step_acc variant (0 registers + paired lines, 1 accumulator in LDS,
-  // 2 registers + one line at a time; k_steps.hip)
-  // defaults (round 4): the accumulator in LDS at one wave per SIMD -- alone 4.64-4.70 ms per
-  // C2 launch against 6.04-6.10 for one line at a time at 2 waves/SIMD (which spilled 1,408
-  // B/lane: 18.3 GB of traffic per launch, 13.9x the algorithmic bytes; now 2.6 GB, 2.0x), the
-  // pipeline 3.55-3.62 vs 3.54-3.57 M sets/s, three interleaved runs each
-  // (profiles/r04/step_ab/).  Round 3 had measured 2/2 ahead of 2/1 (profiles/ab_r03/ab_r03s).
-  // Round 5, in the final pipeline (merged-check program, two-phase flow): one line at a time
-  // at 2 waves/SIMD (LB_STEP_MODE=2 LB_STEP_WAVES=2) measured ahead -- 3.61-3.67 M (mean 3.650
-  // over 5 runs) against the LDS build's 3.53-3.61 M (mean 3.569) -- but alone it takes 5.7 ms
-  // against 4.4-4.5 and moves 18.4 GB per launch (13.9x its algorithmic bytes: spills) against
-  // 2.6 GB (profiles/r05/knobs/, final/pmc_traffic_r05s3.json); the LDS build stays the default
-  // until a 2-wave build without the spills exists (half the accumulator in LDS: 18 KB a
-  // workgroup, 8 per CU)
-  int step_mode = 1;
-  int step_waves = 1;  // LB_STEP_WAVES: occupancy target of k_step_acc (1 or 2)
   // LB_STAGE_EVENTS=0: no per-stage timing events (two HIP calls per kernel of the
   // submission; the N-API addon sets it, lb_last_stage_times is then empty)
   bool stage_events = true;
-  // per-request tails: one wave per request (k_lines_S + k_tail, wave-cooperative
-  // Fp12) or LB_TAIL=lane: one lane per request (k_miller_S + k_final)
-  bool tail_wave = true;
-  // merged check of the whole call first (one tail), per-request tails only
-  // when it fails; used from merge_min_req requests up (LB_MERGE_MIN, 0 = off)
-  uint32_t merge_min_req = 8;
-  // merged calls of at least msm_min_sets sets take S_all from the bucket MSM
-  // (k_msm.hip) instead of per-set ladders (LB_MSM_MIN, 0 = never)
-  uint32_t msm_min_sets = 1025;  // (same probe: from 1025 sets the MSM beats the ladders)
-  // merged steps calls: the level products as lane products + wave-cooperative passes
-  // (k_level_part / k_level_wc) instead of k_level_prod's one-lane LDS tree (LB_LEVEL=0)
-  bool level_wc = true;
-  // lone calls: the MSM's bucket sums on LB_MSM_BLANES lanes per bucket and its bit sums on 256
-  // threads (LB_MSM_LANES=0: one lane per bucket and one wave per bit, round 5, always), the
-  // merged-check program on 64 rows (LB_WIDE_TAIL=0: 32 rows always)
-  bool msm_lanes = true;
-  bool wide_tail = true;
-  bool msm_bits_lp = true;  // (LB_MSM_BITS_LP=0: a lone call's bit sums by k_msm_bits' 256 threads)
-  uint32_t step_split = 0;  // LB_STEP_SPLIT: 1, 2 or 4 lanes per set always (0: by size, lone calls only)
   // same-message packages of at most LB_SM_DEC_MAX signatures decode them as round programs
   // (k_lp_dec; LB_SM_LP_DECODE=0: k_decode_sigs always)
   bool sm_lp_decode = true;
@@ -352,19 +303,6 @@ struct lb_ctx {
   // reference snapshot's) or LB_SM_RANDOMIZED (sum s_i pk_i / sum s_i sig_i, k_smrand.hip);
   // lb_set_same_message_mode, or LB_SM_RANDOMIZED=1 in the environment at lb_create
   uint32_t sm_mode = LB_SM_PLAIN;
-  // lone pipeline calls of at most LB_LP_DEC_MAX sets decode their signatures the same way
-  // (LB_LP_DECODE=0: k_decode_sigs)
-  bool lp_decode = true;
-  bool lp_hash_finish = true;  // (LB_LP_HASH_FINISH: the same calls' hash finish as round programs)
-  bool msm_short = true;  // (LB_MSM_SHORT: a lone mid-size call's MSM chunks of LB_MSM_T_LONE entries)
-  uint32_t msm_short_max = 16384u, msm_t_lone = LB_MSM_T_LONE;  // (LB_MSM_SHORT_MAX / LB_MSM_T_LONE probes)
-  // (the lone-call round-program size bounds; env LB_LP_DEC_MAX / LB_LP_HF_MAX / LB_LP_LINES_MAX probe others)
-  uint32_t lp_dec_max = LB_LP_DEC_MAX, lp_hf_max = LB_LP_HF_MAX, lp_lines_max = LB_LP_LINES_MAX;
-  // (LB_LP_HASH_FULL: lone calls of at most this many sets run hash_to_G2's whole curve part as one
-  // program per set, k_lp_hash -- profiles/r06/orgs_probe_r06hf3.json; 0: never)
-  uint32_t lp_hash_full = 2048;
-  uint32_t lp_narrow = 1;  // (LB_LP_NARROW=1: the hash-finish program on LB_LP_NARROW_ROWS rows, default; 0: 16 rows)
-  bool lp_lines = true;  // (LB_LP_LINES: a lone steps call's lines as round programs, up to LB_LP_LINES_MAX sets)
   // device-resident pubkey table (index2pubkey mirror, lb_pubkey_table_*)
   g1a* d_table = nullptr;
   uint32_t table_n = 0, table_cap = 0;
@@ -387,20 +325,8 @@ struct lb_ctx {
   uint8_t* h_aux = nullptr;
   size_t aux_cap = 0;
   // latency path: the round programs in device memory (uploaded on first use);
-  // calls of at most lp_max_sets sets run it instead of the throughput pipeline
-  // (LB_LP_MAX, lb_set_latency_path; 0 = never)
+  // calls of at most cfg.lp_max_sets sets run it instead of the throughput pipeline
   uint32_t* d_lp = nullptr;
-  uint32_t lp_max_sets = 1024;
-  uint32_t lp_lone_max = 896;  // (LB_LP_LONE_MAX, 0 = off: lone calls above it take the pipeline, run_pipeline)
-  bool lp_explicit = false;    // (the bound set by lb_set_latency_path / LB_LP_MAX: no lone rule)
-  // the merged check of a steps + MSM call as a round program (k_lp_mtail: S_all from the
-  // MSM's bit sums, Miller(-g1, S_all), final exponentiation on one workgroup) instead of
-  // msm_final + lines of S_all + the one-wave k_tail (LB_MTAIL=0: the one-wave chain)
-  bool mtail_lp = true;
-  // LB_RTAIL (default 1): a failed merged check's per-request tails (Miller(-g1, S_k), F_k times
-  // it, final exponentiation) as one round program per request (k_lp_rtail) instead of one-lane
-  // lines of S_k (k_lines_S) + the one-wave chain (k_tail)
-  bool rtail_lp = true;
   bool gt_lp = true;  // lb_gt_check's final exponentiation as a round program (LB_GT_LP=0: one wave)
   int hw_queues = 0;  // hardware queues this context opens (priced by lb_create's guard)
   int q_plain = 0, q_high = 0, q_masked = 0;  // its streams in the process tally (g_q_*)
@@ -506,15 +432,16 @@ int ensure_pin(lb_ctx* ctx, Slot& sl, size_t bytes) {
   } while (0)
 #define LB_STAGE(name, s, kern, grid, block, ...) LB_STAGE_ON(name, sl.st[s], kern, grid, block, __VA_ARGS__)
 
-#define LB_LAUNCH(kern, grid, block, ...)                                                  \
+// A launch without a stage of its own (no timing events, no name in lb_last_stage_times):
+// the launch and its error check in one, so no launch goes unchecked.
+#define LB_ENQUEUE(strm, kern, grid, block, ...)                                           \
   do {                                                                                     \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, ctx->stream, __VA_ARGS__);       \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, strm, __VA_ARGS__);              \
     LB_HIP(hipGetLastError());                                                             \
   } while (0)
+#define LB_LAUNCH(kern, grid, block, ...) LB_ENQUEUE(ctx->stream, kern, grid, block, __VA_ARGS__)
 
 int lp_ensure(lb_ctx* ctx);
-static uint32_t level_blocks(uint32_t n_sets, uint32_t n_req, bool wide);
-static uint32_t step_split_for(uint32_t n_sets);
 int slot_copy(lb_ctx* ctx, Slot& sl, void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t st);
 
 // The latency path (k_lp.hip) for a small call: pubkeys -> per-set inputs -> one
@@ -588,15 +515,6 @@ int stream_wait(lb_ctx* ctx, Slot& sl, int from, int to, int ev) {
   return LB_OK;
 }
 
-// Core pipeline on device-resident inputs (all pointers are device pointers),
-// as a two-stream DAG inside the slot:
-//   A: flags -> pubkeys -> r_i pk_i -> [evPK] -> decode sigs -> r_i sig_i -> S_k (tree)
-//      -> Miller(-g1, S_k) -> [wait B] -> per-request product (tree) -> final exp
-//   B: hash_to_G2 (two lanes per message) -> [wait evPK] -> lines of (r_i pk_i, H_i)
-// with the Miller values accumulated per request from the stored lines
-// (k_miller_acc, several pairs per lane sharing the Fp12 squarings); the
-// original one-pair-per-lane Miller (k_miller_sets + k_prod_tree) remains
-// selectable with LB_MILLER=lane for comparison.
 // Tails of a call (after the per-request products F_k): with a merged check,
 // the per-request tails run only when d_mflag[0] == 0 (k_lines_S / k_tail skip
 // themselves otherwise); without one, every request runs its tail.
@@ -621,9 +539,8 @@ int run_tails(lb_ctx* ctx, Slot& sl) {
                  (const uint8_t*)p.d_bad, p.d_F, (const uint8_t*)p.d_mflag);
     }
     if (p.d_rt_in) {
-      hipLaunchKernelGGL(k_rtail_prep, dim3((p.n_req * LB_RTAIL_NIN + 255) / 256), dim3(256), 0, sl.st[0], p.n_req,
-                         (const fp12*)p.d_F, (const g2a*)p.d_S, p.d_rt_in, p.d_rt_fl);
-      LB_HIP(hipGetLastError());
+      LB_ENQUEUE(sl.st[0], k_rtail_prep, (p.n_req * LB_RTAIL_NIN + 255) / 256, 256, p.n_req, (const fp12*)p.d_F,
+                 (const g2a*)p.d_S, p.d_rt_in, p.d_rt_fl);
       LB_STAGE("rtail", 0, k_lp_rtail, p.n_req, LB_LP_TPB, ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_RTAIL].off, p.n_req,
                (const uint32_t*)p.d_rt_in, (const uint32_t*)p.d_rt_fl, (const uint8_t*)p.d_bad, p.d_valid,
                (const uint8_t*)p.d_mflag);
@@ -631,9 +548,8 @@ int run_tails(lb_ctx* ctx, Slot& sl) {
       LB_STAGE("tail", 0, k_tail, p.n_req, TPB, p.n_req, p.n_pairs, p.n_sets, (const uint32_t*)p.d_lines,
                (const fp12*)p.d_F, (const uint8_t*)p.d_bad, p.d_valid, (const uint8_t*)p.d_mflag);
     }
-    hipLaunchKernelGGL(k_merge_stats, dim3(1), dim3(TPB), 0, sl.st[0], p.n_req, p.d_req_off, (const uint8_t*)p.d_bad,
-                       (const uint8_t*)p.d_mflag, p.d_mstats);
-    LB_HIP(hipGetLastError());
+    LB_ENQUEUE(sl.st[0], k_merge_stats, 1, TPB, p.n_req, p.d_req_off, (const uint8_t*)p.d_bad,
+               (const uint8_t*)p.d_mflag, p.d_mstats);
     LB_HIP(hipMemcpyAsync(sl.h_stats, p.d_mstats, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.st[0]));
   } else if (p.tail_wave) {
     LB_STAGE("tail", 0, k_tail, p.n_req, TPB, p.n_req, p.n_pairs, p.n_sets, (const uint32_t*)p.d_lines,
@@ -645,559 +561,575 @@ int run_tails(lb_ctx* ctx, Slot& sl) {
   return LB_OK;
 }
 
-// lone calls of lp_lone_max < n_sets <= lp_max_sets leave the latency path for the pipeline
-// (run_pipeline's lone_mid; the synchronous entry points then take slot 0's two-stream DAG)
-static bool lp_lone_rule(const lb_ctx* ctx, uint32_t n_sets) {
-  return !ctx->lp_explicit && ctx->lp_lone_max && n_sets > ctx->lp_lone_max && n_sets <= ctx->lp_max_sets;
-}
-
 static bool any_slot_busy(const lb_ctx* ctx) {
   for (int s = 0; s <= ctx->n_slots; s++)
     if (ctx->slots[s].busy) return true;
   return false;
 }
 
-int run_pipeline(lb_ctx* ctx, Slot& sl, uint32_t n_req, uint32_t n_sets, const uint32_t* d_req_off,
-                 const uint8_t* d_pks, const uint32_t* d_pk_off, const uint32_t* d_pk_idx, const uint8_t* d_msgs, const uint8_t* d_sigs,
-                 const uint32_t* d_sig_off, const uint8_t* d_seed, uint8_t* d_valid, uint8_t* d_req_err,
-                 uint8_t* d_set_status, Bump& ws, uint8_t* d_partial = nullptr, const g2j* d_sig_pre = nullptr,
-                 const uint8_t* d_sst_pre = nullptr) {
-  // d_sig_pre / d_sst_pre: signatures already decoded and validated (same-message
-  // phase 2): no k_decode_sigs, d_sigs / d_sig_off unused
-  const bool partial = d_partial != nullptr;
-  bool lone = true;  // (no other slot busy: the GPU is this call's)
+// the GPU is this call's: no other throughput slot busy, the slots lent to the call apart
+static bool call_is_lone(const lb_ctx* ctx, const Slot& sl) {
   for (int s = 0; s < ctx->n_slots; s++)
-    if (&ctx->slots[s] != &sl && ctx->slots[s].busy && ctx->slots[s].lent_to != &sl) lone = false;
-  // a lone call of lp_lone_max < n_sets <= lp_max_sets runs the pipeline's steps + MSM + merged-check
-  // program instead of the latency path (~7.0 ms flat from ~400 sets against the latency path's
-  // 7.2 / 8.0 ms at 896 / 1,024 sets, profiles/r06/orgs_probe_r06lp2.json), merged whatever its
-  // request count; not when the latency-path bound was set explicitly (lb_set_latency_path, LB_LP_MAX)
-  const bool lone_mid = !partial && !d_sig_pre && lone && &sl != &ctx->prio() && lp_lone_rule(ctx, n_sets) &&
-                        ctx->miller_mode == 0 && ctx->tail_wave && ctx->acc_steps;
-  if (!partial && !d_sig_pre && n_sets <= ctx->lp_max_sets && !lone_mid) {
-    sl.h_stats[0] = sl.h_stats[1] = 0;
-    return run_lp(ctx, sl, n_req, n_sets, d_req_off, d_pks, d_pk_off, d_pk_idx, d_msgs, d_sigs, d_sig_off, d_seed,
-                  d_valid, d_req_err, d_set_status, ws);
+    if (&ctx->slots[s] != &sl && ctx->slots[s].busy && ctx->slots[s].lent_to != &sl) return false;
+  return true;
+}
+
+static_assert(sizeof(g2j) == SZ_G2J && sizeof(g1j) == SZ_G1J && sizeof(g2a) == SZ_G2A && sizeof(fp12) == SZ_FP12 &&
+                  LB_GT_BYTES == SZ_FP12,
+              "bls_plan.h lays the workspace out with these record sizes");
+
+// A pipeline call's device pointers: what the caller passed, and the workspace buffers of
+// its layout (bls_plan.h PipeBuf, same order; nullptr: the plan has no such buffer).
+struct PipeBufs {
+  const uint32_t* req_off;
+  const uint8_t* pks;
+  const uint32_t *pk_off, *pk_idx;
+  const uint8_t *msgs, *sigs;
+  const uint32_t* sig_off;
+  const uint8_t* seed;
+  uint8_t *valid, *req_err, *partial;
+  g2j *sig, *rsig, *q, *h;
+  g1j *pk, *rpk;
+  fp12* f;  // per-set Miller values (lane / wave organisations)
+  uint32_t* lines;
+  uint8_t *single, *pk_st, *sig_st;
+  g2a* S;
+  fp12 *fS, *F;
+  uint32_t *rt_in, *rt_fl;
+  uint8_t* bad;
+  g2a* Sall;
+  fp12* Fall;
+  uint8_t* mflag;
+  uint32_t* mstats;
+  uint32_t *mkeys, *msorted, *mhist;
+  g2j *mcsum, *mbsum, *mG;
+  uint32_t *rhist, *rgt, *rowoff, *rpos, *rinv, *rmeta, *G;
+  fp12* Fparts;
+  uint32_t *dec_in, *dec_fl, *dec_out, *dec_ofl;
+  uint8_t* dec_pre;
+  uint32_t *hf_in, *hf_out, *ll_in, *ll_out;
+  fp12 *Pl, *lvA, *lvB;
+  uint8_t *lhA, *lhB;
+  uint32_t *mt_in, *mt_out, *mb_in0, *mb_in1, *mb_in2;
+  fp12* Fx;
+  uint32_t* off2;
+  fp12* acc_F;
+  uint8_t *acc_bad, *acc_err;
+  Rows rows;
+  hipStream_t ts;  // the merged check's stream: the slot's own, or the shared high-priority one (LB_TAIL_PRIO=1)
+};
+
+template <class T>
+static T* buf_at(char* base, const PipeLayout& L, PipeBuf b) {
+  return L.has(b) ? reinterpret_cast<T*>(base + L.off[b]) : nullptr;
+}
+
+static void bind_workspace(PipeBufs& b, char* base, const PipeLayout& L, uint32_t lsplit) {
+  b.sig = buf_at<g2j>(base, L, PB_SIG);
+  b.rsig = buf_at<g2j>(base, L, PB_RSIG);
+  b.q = buf_at<g2j>(base, L, PB_Q);
+  b.h = buf_at<g2j>(base, L, PB_H);
+  b.pk = buf_at<g1j>(base, L, PB_PK);
+  b.rpk = buf_at<g1j>(base, L, PB_RPK);
+  b.f = buf_at<fp12>(base, L, PB_F_SETS);
+  b.lines = buf_at<uint32_t>(base, L, PB_LINES);
+  b.single = buf_at<uint8_t>(base, L, PB_SINGLE);
+  b.pk_st = buf_at<uint8_t>(base, L, PB_PK_ST);
+  b.sig_st = buf_at<uint8_t>(base, L, PB_SIG_ST);
+  b.S = buf_at<g2a>(base, L, PB_S);
+  b.fS = buf_at<fp12>(base, L, PB_FS);
+  b.F = buf_at<fp12>(base, L, PB_F);
+  b.rt_in = buf_at<uint32_t>(base, L, PB_RT_IN);
+  b.rt_fl = buf_at<uint32_t>(base, L, PB_RT_FL);
+  b.bad = buf_at<uint8_t>(base, L, PB_BAD);
+  b.Sall = buf_at<g2a>(base, L, PB_SALL);
+  b.Fall = buf_at<fp12>(base, L, PB_FALL);
+  b.mflag = buf_at<uint8_t>(base, L, PB_MFLAG);
+  b.mstats = buf_at<uint32_t>(base, L, PB_MSTATS);
+  b.mkeys = buf_at<uint32_t>(base, L, PB_MKEYS);
+  b.msorted = buf_at<uint32_t>(base, L, PB_MSORTED);
+  b.mhist = buf_at<uint32_t>(base, L, PB_MHIST);
+  b.mcsum = buf_at<g2j>(base, L, PB_MCSUM);
+  b.mbsum = buf_at<g2j>(base, L, PB_MBSUM);
+  b.mG = buf_at<g2j>(base, L, PB_MG);
+  b.rhist = buf_at<uint32_t>(base, L, PB_RHIST);
+  b.rgt = buf_at<uint32_t>(base, L, PB_RGT);
+  b.rowoff = buf_at<uint32_t>(base, L, PB_ROWOFF);
+  b.rpos = buf_at<uint32_t>(base, L, PB_RPOS);
+  b.rinv = buf_at<uint32_t>(base, L, PB_RINV);
+  b.rmeta = buf_at<uint32_t>(base, L, PB_RMETA);
+  b.G = buf_at<uint32_t>(base, L, PB_G);
+  b.Fparts = buf_at<fp12>(base, L, PB_FPARTS);
+  b.dec_in = buf_at<uint32_t>(base, L, PB_DEC_IN);
+  b.dec_fl = buf_at<uint32_t>(base, L, PB_DEC_FL);
+  b.dec_out = buf_at<uint32_t>(base, L, PB_DEC_OUT);
+  b.dec_ofl = buf_at<uint32_t>(base, L, PB_DEC_OFL);
+  b.dec_pre = buf_at<uint8_t>(base, L, PB_DEC_PRE);
+  b.hf_in = buf_at<uint32_t>(base, L, PB_HF_IN);
+  b.hf_out = buf_at<uint32_t>(base, L, PB_HF_OUT);
+  b.ll_in = buf_at<uint32_t>(base, L, PB_LL_IN);
+  b.ll_out = buf_at<uint32_t>(base, L, PB_LL_OUT);
+  b.Pl = buf_at<fp12>(base, L, PB_PL);
+  b.lvA = buf_at<fp12>(base, L, PB_LVA);
+  b.lvB = buf_at<fp12>(base, L, PB_LVB);
+  b.lhA = buf_at<uint8_t>(base, L, PB_LHA);
+  b.lhB = buf_at<uint8_t>(base, L, PB_LHB);
+  b.mt_in = buf_at<uint32_t>(base, L, PB_MT_IN);
+  b.mt_out = buf_at<uint32_t>(base, L, PB_MT_OUT);
+  b.mb_in0 = buf_at<uint32_t>(base, L, PB_MB_IN0);
+  b.mb_in1 = buf_at<uint32_t>(base, L, PB_MB_IN1);
+  b.mb_in2 = buf_at<uint32_t>(base, L, PB_MB_IN2);
+  b.Fx = buf_at<fp12>(base, L, PB_FX);
+  b.off2 = buf_at<uint32_t>(base, L, PB_OFF2);
+  b.acc_F = buf_at<fp12>(base, L, PB_ACC_F);
+  b.acc_bad = buf_at<uint8_t>(base, L, PB_ACC_BAD);
+  b.acc_err = buf_at<uint8_t>(base, L, PB_ACC_ERR);
+  b.partial = buf_at<uint8_t>(base, L, PB_PARTIAL);
+  b.rows = Rows{b.rowoff, b.rinv, b.rpos, b.rmeta, lsplit};
+}
+
+// ---- kernel variants by plan field ----------------------------------------------------------
+static decltype(&k_lines<1>) lines_kernel(const PipePlan& p) { return p.lines_W == 1 ? k_lines<1> : k_lines<2>; }
+static decltype(&k_lines_rows<1>) lines_rows_kernel(const PipePlan& p) {
+  return p.lines_W == 1 ? k_lines_rows<1> : k_lines_rows<2>;
+}
+static decltype(&k_step_acc<0, 1>) step_acc_kernel(const PipePlan& p) {
+  if (p.step_M == 1) return k_step_acc<1, 1>;
+  if (p.step_M == 2) return p.step_W == 2 ? k_step_acc<2, 2> : k_step_acc<2, 1>;
+  return p.step_W == 2 ? k_step_acc<0, 2> : k_step_acc<0, 1>;
+}
+static decltype(&k_miller_acc<64>) miller_acc_kernel(const PipePlan& p) {
+  return p.acc_lpr == 16 ? k_miller_acc<16> : p.acc_lpr == 32 ? k_miller_acc<32> : k_miller_acc<64>;
+}
+
+static const uint32_t* lp_prog(const lb_ctx* ctx, int prog) { return ctx->d_lp + LB_LP_PROGS[prog].off; }
+
+// ---- the stages, in the order run_pipeline enqueues them ------------------------------------
+// Each tests plan fields only.  Stream 0 carries the call's spine, stream 1 the hash and the lines.
+
+// hash_to_G2 of every message (stream 1): two lanes per message and the finish, the finish as
+// round programs, or the whole curve part as one program per set
+static int enqueue_hash(lb_ctx* ctx, Slot& sl, const PipePlan& p, const PipeBufs& b) {
+  const uint32_t n_sets = p.n_sets;
+  if (p.hash == HASH_NONE) return LB_OK;
+  if (p.hash == HASH_FULL_LP) {
+    LB_STAGE("hash_finish", 1, k_hu_prep, blocks_for(n_sets, 256), 256u, n_sets, b.msgs, b.hf_in);
+    LB_STAGE("hash_finish", 1, k_lp_hash, n_sets, LB_LP_NARROW_ROWS * 16u, lp_prog(ctx, LB_LP_PROG_HASH_FULL), n_sets,
+             (const uint32_t*)b.hf_in, b.hf_out);
+    LB_STAGE("hash_finish", 1, k_hf_finish, blocks_for(n_sets * 6u, 256), 256u, n_sets, (const uint32_t*)b.hf_out, b.h);
+    return LB_OK;
   }
-  const uint32_t ns = n_sets ? n_sets : 1;
-  g2j* d_sig = d_sig_pre ? const_cast<g2j*>(d_sig_pre) : ws.take<g2j>(ns);
-  g2j* d_rsig = ws.take<g2j>(ns);
-  g2j* d_q = ws.take<g2j>(2 * (size_t)ns);
-  g2j* d_h = ws.take<g2j>(ns);
-  g1j* d_pk = ws.take<g1j>(ns);
-  g1j* d_rpk = ws.take<g1j>(ns);
-  const bool by_lines = ctx->miller_mode == 2 || (ctx->miller_mode == 0 && n_sets >= ctx->lines_min_sets) || lone_mid;
-  const bool by_wave =
-      !by_lines && (ctx->miller_mode == 3 || (ctx->miller_mode == 0 && n_sets <= ctx->wave_max_sets));
-  fp12* d_f = by_lines ? nullptr : ws.take<fp12>(ns);  // per-set Miller values (lane / wave modes)
-  // a two-phase call always merges (its partial is the merged product) and uses the wave tails
-  const bool tail_wave = ctx->tail_wave || partial;
-  // stored lines: set pairs [0, n_sets) (lines mode), S pairs [n_sets, n_sets + n_req) (wave tails)
-  const bool merged = partial || (tail_wave && ctx->merge_min_req && n_req >= ctx->merge_min_req) || lone_mid;
-  const uint32_t n_pairs = n_sets + n_req + (merged ? 1u : 0u);  // + the merged pair (-g1, S_all)
-  const bool use_msm = merged && n_sets && ctx->msm_min_sets && (n_sets >= ctx->msm_min_sets || lone_mid);
-  // a lone call on an otherwise idle GPU splits every request of the Miller
-  // accumulation in two halves: twice the waves (one per SIMD for a 65,536-set
-  // call instead of one per two SIMDs) at the price of the halves' separate
-  // Fp12 squarings; with other calls in flight the idle SIMDs run their stages
-  // instead and the work-efficient form is kept (LB_ACC_SPLIT=0|1 forces one)
-  // steps organisation (k_steps.hip): no split (a request already has one lane per set)
-  const bool steps = by_lines && tail_wave && n_sets && ctx->acc_steps;
-  const bool split = by_lines && !steps && (ctx->acc_split == 1 || (ctx->acc_split < 0 && lone && n_req >= 64));
-  // merged pair (-g1, S_all) with S_all from the MSM: without a split its Miller
-  // value is one extra workgroup of k_miller_acc (fold; its 512 request waves
-  // leave SIMDs free), otherwise its lines are stored right after the MSM, on
-  // stream 0 beside stream 1's hash/lines (lines_all), and k_tail multiplies it in
-  const bool fold = use_msm && by_lines && !split && !steps;
-  // merged check as a round program (k_lp_mtail): S_all, its Miller value and the final
-  // exponentiation from the MSM's bit sums and the 63 level products (their Horner chain folded in)
-  const bool mtail = steps && use_msm && merged && ctx->mtail_lp;
-  // a lone call's serial tail in its wide forms (the GPU otherwise idle: latency is what counts):
-  // the merged-check program on LB_LP_MTAIL_ROWS rows, the MSM's sums over more lanes.  With other
-  // calls in flight the narrow forms, whose smaller workgroups wait for less of a CU (C2 3.62 vs
-  // 3.67 / 3.68 M sets/s with either wide form in every call, profiles/r06/ab_r06k/)
-  const bool mt_wide = lone && ctx->wide_tail;
-  const uint32_t mt_tpb = mt_wide ? LB_LP_MTAIL_ROWS * 16u : (uint32_t)LB_LP_TPB;
-  const bool msm_wide = lone && ctx->msm_lanes;
-  // (and its bit sums as round programs: 9 dependent one-lane additions -> 3 launches of ~10-16 rounds)
-  const bool bits_lp = msm_wide && mtail && ctx->msm_bits_lp;
-  if (mtail) LB_TRY(lp_ensure(ctx));
+  LB_STAGE("hash_half", 1, k_hash_half, blocks_for(2 * n_sets), TPB, n_sets, b.msgs, b.q);
+  if (p.hash == HASH_FINISH_LP) {  // clear_cofactor(Q0 + Q1) as round programs, k_lp_hf
+    LB_STAGE("hash_finish", 1, k_hf_prep, blocks_for(n_sets * 12u, 256), 256u, n_sets, (const g2j*)b.q, b.hf_in);
+    LB_STAGE("hash_finish", 1, k_lp_hf, n_sets, (p.hf_narrow ? LB_LP_NARROW_ROWS : LB_LP_HF_ROWS) * 16u,
+             lp_prog(ctx, p.hf_narrow ? LB_LP_PROG_HASH_FINISH_NARROW : LB_LP_PROG_HASH_FINISH), n_sets,
+             (const uint32_t*)b.hf_in, b.hf_out);
+    LB_STAGE("hash_finish", 1, k_hf_finish, blocks_for(n_sets * 6u, 256), 256u, n_sets, (const uint32_t*)b.hf_out, b.h);
+  } else {
+    LB_STAGE("hash_finish", 1, k_hash_finish, blocks_for(n_sets), TPB, n_sets, b.q, b.h);
+  }
+  return LB_OK;
+}
+
+// request flags, and for the steps organisation the size-descending order of the requests and
+// the row offsets (before stream 1's lines)
+static int enqueue_row_order(lb_ctx* ctx, Slot& sl, const PipePlan& p, const PipeBufs& b) {
+  LB_STAGE("req_flags", 0, k_req_flags, blocks_for(p.n_req), TPB, p.n_req, b.req_off, b.single);
+  if (!p.steps) return LB_OK;
+  uint32_t* d_rcur = b.rhist + (p.ns + 1);
+  LB_HIP(hipMemsetAsync(b.rhist, 0, 2 * ((size_t)p.ns + 1) * sizeof(uint32_t), sl.st[0]));
+  LB_ENQUEUE(sl.st[0], k_rows_hist, blocks_for(p.n_req, 256), 256, p.n_req, b.req_off, b.rhist);
+  LB_ENQUEUE(sl.st[0], k_rows_scan, 1, 1024, p.n_sets, (const uint32_t*)b.rhist, b.rgt, b.rowoff, b.rmeta);
+  LB_ENQUEUE(sl.st[0], k_rows_pos, blocks_for(p.n_req, 256), 256, p.n_req, b.req_off, (const uint32_t*)b.rgt, d_rcur,
+             b.rpos, b.rinv);
+  return LB_OK;
+}
+
+// PublicKey.fromBytes + aggregate, then r_i pk_i
+static int enqueue_pubkeys(lb_ctx* ctx, Slot& sl, const PipePlan& p, const PipeBufs& b) {
+  const uint32_t n_sets = p.n_sets;
+  if (!n_sets) return LB_OK;
+  const PkSource src{b.pks, b.pk_idx, ctx->d_table, ctx->table_n};
+  LB_STAGE("pubkeys", 0, k_pubkeys_single, blocks_for(n_sets), TPB, n_sets, src, b.pk_off, b.pk, b.pk_st);
+  if (b.pk_off)
+    // one wave per set, grid-stride: enough waves that every aggregate of a
+    // C4/C5-sized call (thousands of committee sets) gets its own
+    LB_STAGE("pubkeys_agg", 0, k_pubkeys_agg, n_sets < 16384u ? n_sets : 16384u, TPB, n_sets, src, b.pk_off, b.pk,
+             b.pk_st);
+  LB_STAGE("scalar_pk", 0, k_scalar_pk, blocks_for(n_sets), TPB, n_sets, b.seed, (const g1j*)b.pk,
+           (const uint8_t*)b.single, b.pk_st, b.rpk);
+  return LB_OK;
+}
+
+// the lines of (r_i pk_i, H_i) or the per-set Miller values (stream 1)
+static int enqueue_lines(lb_ctx* ctx, Slot& sl, const PipePlan& p, const PipeBufs& b) {
+  const uint32_t n_sets = p.n_sets, n_pairs = p.n_pairs;
+  if (p.lines == LINES_LP) {
+    // (a lone mid-size call: each slot's 68 lines as a round program, k_lp_lines)
+    LB_STAGE("lines", 1, k_lines_prep, blocks_for(n_sets * 9u, 256), 256u, n_sets, b.rows, b.req_off, (const g1j*)b.rpk,
+             (const g2j*)b.h, b.ll_in);
+    LB_STAGE("lines", 1, k_lp_lines, n_sets, LB_LP_HF_ROWS * 16u, lp_prog(ctx, LB_LP_PROG_LINES), n_sets,
+             (const uint32_t*)b.ll_in, b.ll_out);
+    LB_STAGE("lines", 1, k_lines_store, (uint32_t)(((size_t)n_sets * LB_MILLER_LINES * 72 + 255) / 256), 256u, n_sets,
+             n_pairs, (const uint32_t*)b.ll_out, b.lines);
+  } else if (p.lines == LINES_ROWS) {
+    LB_STAGE("lines", 1, lines_rows_kernel(p), blocks_for(n_sets), TPB, n_sets, n_pairs, b.rows, b.req_off,
+             (const g1j*)b.rpk, b.h, b.lines);
+  } else if (p.lines == LINES_PLAIN) {
+    LB_STAGE("lines", 1, lines_kernel(p), blocks_for(n_sets), TPB, n_sets, n_pairs, 0u, (const g1j*)b.rpk,
+             (const g2j*)b.h, b.lines);
+  }
+  if (p.miller_wave)
+    LB_STAGE("miller_wave", 1, k_pair_wc, n_sets, TPB, n_sets, n_pairs, (const uint32_t*)b.lines, b.f);
+  else if (p.miller_sets)
+    LB_STAGE("miller_sets", 1, k_miller_sets, blocks_for(n_sets), TPB, n_sets, (const g1j*)b.rpk, (const g2j*)b.h, b.f);
+  return LB_OK;
+}
+
+// Signature.fromBytes(validate=true), and r_i sig_i where the MSM does not take their sum
+static int enqueue_decode(lb_ctx* ctx, Slot& sl, const PipePlan& p, const PipeBufs& b) {
+  const uint32_t n_sets = p.n_sets;
+  if (!n_sets) return LB_OK;
+  if (p.decode == DECODE_LP) {
+    // (a lone mid-size call: the signatures' decode as round programs, k_lp_dec -- its one-lane
+    // chain is ~5.7 ms whatever the count below the GPU's width)
+    LB_STAGE("decode_sigs", 0, k_sm_dec_prep, blocks_for(n_sets, 256), 256u, n_sets, b.sigs, b.sig_off, b.dec_in,
+             b.dec_fl, b.dec_pre);
+    LB_STAGE("decode_sigs", 0, k_lp_dec, n_sets, LB_LP_DEC_ROWS * 16u, lp_prog(ctx, LB_LP_PROG_SIG_DECODE), n_sets,
+             (const uint32_t*)b.dec_in, (const uint32_t*)b.dec_fl, b.dec_out, b.dec_ofl);
+    LB_STAGE("decode_sigs", 0, k_sm_dec_finish, blocks_for(n_sets, 256), 256u, n_sets, (const uint8_t*)b.dec_pre,
+             (const uint32_t*)b.dec_in, (const uint32_t*)b.dec_fl, (const uint32_t*)b.dec_out,
+             (const uint32_t*)b.dec_ofl, b.sig, b.sig_st, (const uint8_t*)b.single);
+  } else if (p.decode == DECODE_PLAIN) {
+    LB_STAGE("decode_sigs", 0, k_decode_sigs, blocks_for(n_sets), TPB, n_sets, b.sigs, b.sig_off,
+             (const uint8_t*)b.single, b.sig, b.sig_st);
+  }
+  if (!p.use_msm)
+    LB_STAGE("scalar_sig", 0, k_scalar_sig, blocks_for(n_sets), TPB, n_sets, b.seed, (const g2j*)b.sig,
+             (const uint8_t*)b.sig_st, b.rsig, (const uint8_t*)nullptr);
+  return LB_OK;
+}
+
+// request status of the steps organisation (k_miller_acc's side reduction in the pairs organisation)
+static int enqueue_req_status(lb_ctx* ctx, Slot& sl, const PipePlan& p, const PipeBufs& b) {
+  if (p.steps)
+    LB_STAGE("req_status", 0, k_req_status, p.n_req < 4096u ? p.n_req : 4096u, TPB, p.n_req, b.req_off,
+             (const uint8_t*)b.sig_st, (const uint8_t*)b.pk_st, b.bad, b.req_err);
+  return LB_OK;
+}
+
+// S_all = sum r_i sig_i over the good requests' sets: one bucket MSM (k_msm.hip)
+static int enqueue_msm(lb_ctx* ctx, Slot& sl, const PipePlan& p, const PipeBufs& b) {
+  const uint32_t n_req = p.n_req, n_sets = p.n_sets, n_pairs = p.n_pairs;
+  uint32_t* d_off = b.mhist + (LB_MSM_BUCKETS + 1);
+  uint32_t* d_coff = d_off + (LB_MSM_BUCKETS + 1);
+  uint32_t* d_cur = d_coff + (LB_MSM_BUCKETS + 1);
+  LB_HIP(hipMemsetAsync(b.mhist, 0, (LB_MSM_BUCKETS + 1) * sizeof(uint32_t), sl.st[0]));
+  LB_STAGE("msm_digits", 0, k_msm_scalars, n_req, TPB, n_req, b.req_off, b.seed, (const uint64_t*)nullptr,
+           (const g2j*)b.sig, (const uint8_t*)b.sig_st, (const uint8_t*)b.pk_st, b.mkeys, b.mhist);
+  LB_ENQUEUE(sl.st[0], k_msm_scan, 1, 1024, (const uint32_t*)b.mhist, d_off, d_coff, d_cur, p.msm_T);
+  LB_ENQUEUE(sl.st[0], k_msm_scatter, blocks_for((uint32_t)p.n_ent, 256), 256, (uint32_t)p.n_ent,
+             (const uint32_t*)b.mkeys, (const uint32_t*)d_off, d_cur, b.msorted);
+  LB_STAGE("msm_chunks", 0, k_msm_chunks, blocks_for((uint32_t)p.max_chunks), TPB, (uint32_t)p.max_chunks,
+           (const uint32_t*)d_off, (const uint32_t*)d_coff, (const uint32_t*)b.msorted, (const g2j*)b.sig, b.mcsum,
+           p.msm_T);
+  const uint32_t bl = p.msm_wide ? LB_MSM_BLANES : 1u;
+  LB_STAGE("msm_buckets", 0, k_msm_buckets, blocks_for(LB_MSM_BUCKETS * bl), TPB, (const uint32_t*)d_coff,
+           (const g2j*)b.mcsum, b.mbsum, bl);
+  if (p.bits_lp) {
+    // (a lone call's bit sums as three levels of round programs, 8:1 each; the last writes the
+    // 33 G_p into the merged-check program's input records, so k_mtail_prep skips them)
+    LB_STAGE("msm_bits", 0, k_msm_bits_prep, blocks_for(LB_MSM_BITS_INST * LB_MSM_BITS_GROUP * 6u, 256), 256u,
+             (const g2j*)b.mbsum, b.mb_in0);
+    constexpr uint32_t NI = LB_MSM_BITS_GROUP * 6u;
+    LB_STAGE("msm_bits", 0, k_lp_msm_bits, LB_MSM_BITS_INST, LB_LP_TPB, lp_prog(ctx, LB_LP_PROG_MSM_BITS0),
+             (uint32_t)LB_MSM_BITS_INST, NI, 6u, (const uint32_t*)b.mb_in0, b.mb_in1);
+    LB_STAGE("msm_bits", 0, k_lp_msm_bits, LB_MSM_BITS_INST / 8u, LB_LP_TPB, lp_prog(ctx, LB_LP_PROG_MSM_BITS1),
+             (uint32_t)LB_MSM_BITS_INST / 8u, NI, 6u, (const uint32_t*)b.mb_in1, b.mb_in2);
+    LB_STAGE("msm_bits", 0, k_lp_msm_bits, LB_MSM_POS, LB_LP_TPB, lp_prog(ctx, LB_LP_PROG_MSM_BITS2),
+             (uint32_t)LB_MSM_POS, NI, 6u, (const uint32_t*)b.mb_in2, b.mt_in + (size_t)12 * LB_MTAIL_LEVELS * 16);
+  } else if (p.msm_wide) {
+    LB_STAGE("msm_bits", 0, k_msm_bits<LB_MSM_BITS_TPB>, LB_MSM_POS, LB_MSM_BITS_TPB, (const g2j*)b.mbsum, b.mG);
+  } else {
+    LB_STAGE("msm_bits", 0, k_msm_bits<TPB>, LB_MSM_POS, TPB, (const g2j*)b.mbsum, b.mG);
+  }
+  if (!p.mtail) LB_STAGE("msm_final", 0, k_msm_final, 1u, TPB, (const g2j*)b.mG, b.Sall);
+  // (the merged pair's lines, on stream 0 beside stream 1's hash / lines, unless k_miller_acc
+  // folds the pair in or the merged-check program computes its Miller value)
+  if (!p.fold && !p.mtail)
+    LB_STAGE("lines_all", 0, k_lines_S, 1u, TPB, 1u, n_pairs, n_sets + n_req, (const g2a*)b.Sall, b.lines,
+             (const uint8_t*)nullptr);
+  return LB_OK;
+}
+
+// S_k per request from the per-set ladders; then what the tails need of them before the accumulation
+static int enqueue_sums(lb_ctx* ctx, Slot& sl, const PipePlan& p, const PipeBufs& b) {
+  const uint32_t n_req = p.n_req, n_sets = p.n_sets, n_pairs = p.n_pairs;
+  if (p.use_msm) {
+    LB_TRY(enqueue_msm(ctx, sl, p, b));
+  } else {
+    LB_STAGE("sum_tree", 0, k_sum_tree, n_req, TPB, n_req, b.req_off, (const g2j*)b.rsig, b.S, (const uint8_t*)nullptr);
+    if (p.steps && p.merged) {  // S_all of the good requests and its lines, ahead of the level products
+      LB_STAGE("merge", 0, k_merge, 1u, TPB, n_req, (const g2a*)b.S, (const fp12*)nullptr, (const uint8_t*)b.bad, b.Sall,
+               (fp12*)nullptr, (const fp12*)nullptr);
+      LB_STAGE("lines_all", 0, k_lines_S, 1u, TPB, 1u, n_pairs, n_sets + n_req, (const g2a*)b.Sall, b.lines,
+               (const uint8_t*)nullptr);
+    }
+  }
+  if (p.tail_wave && !p.merged)
+    LB_STAGE("lines_S", 0, k_lines_S, blocks_for(n_req), TPB, n_req, n_pairs, n_sets, (const g2a*)b.S, b.lines,
+             (const uint8_t*)nullptr);
+  else if (!p.tail_wave)
+    LB_STAGE("miller_S", 0, k_miller_S, blocks_for(n_req), TPB, n_req, (const g2a*)b.S, b.fS);
+  return LB_OK;
+}
+
+// steps organisation: step-major lanes, then the level products and their Horner chain (merged)
+// or the per-request Horner values
+static int enqueue_acc_steps(lb_ctx* ctx, Slot& sl, const PipePlan& p, const PipeBufs& b) {
+  const uint32_t n_req = p.n_req, n_sets = p.n_sets, n_pairs = p.n_pairs, lsplit = p.lsplit;
   // (steps + merged: the merged pair's lines come from a one-lane kernel before the
   // accumulation; as an extra workgroup of k_step_acc they measured 4.8 -> 8.2 ms: the
   // 1,025th wave waits for a SIMD of the 1,024 set waves, then runs the 3.4 ms line chain)
-  uint32_t* d_lines =
-      (by_lines || by_wave || tail_wave) ? ws.take<uint32_t>((size_t)n_pairs * LB_MILLER_LINES * 72) : nullptr;
-  uint8_t* d_single = ws.take<uint8_t>(ns);
-  uint8_t* d_pk_st = ws.take<uint8_t>(ns);
-  uint8_t* d_sig_st = d_sst_pre ? const_cast<uint8_t*>(d_sst_pre) : d_set_status ? d_set_status : ws.take<uint8_t>(ns);
-  g2a* d_S = ws.take<g2a>(n_req);
-  fp12* d_fS = ws.take<fp12>(n_req);
-  fp12* d_F = ws.take<fp12>(n_req);
-  // (a merged call's failure path: the per-request tails' round-program inputs, k_lp_rtail)
-  const bool rtail = merged && tail_wave && ctx->rtail_lp;
-  if (rtail) LB_TRY(lp_ensure(ctx));
-  uint32_t* d_rt_in = rtail ? ws.take<uint32_t>((size_t)(n_req ? n_req : 1) * LB_RTAIL_NIN * 16) : nullptr;
-  uint32_t* d_rt_fl = rtail ? ws.take<uint32_t>(n_req ? n_req : 1) : nullptr;
-  uint8_t* d_bad = ws.take<uint8_t>(n_req);
-  g2a* d_Sall = ws.take<g2a>(1);
-  fp12* d_Fall = ws.take<fp12>(1);
-  uint8_t* d_mflag = ws.take<uint8_t>(2);  // [0] merged check passed, [1] constant 0 (req_bad of the merged pair)
-  uint32_t* d_mstats = ws.take<uint32_t>(2);
-  // bucket MSM workspace: keys + sorted entries (2 half-points x W windows per
-  // set), histogram / cursors / offsets, chunk partials, bucket sums, G_p
-  const size_t n_ent = use_msm ? 2 * (size_t)n_sets * LB_MSM_W : 0;
-  // (a lone mid-size call: chunks of LB_MSM_T_LONE entries -- k_msm_chunks' chains are one lane's
-  // mixed additions, 16 of them ~2.5 ms for C5; LB_MSM_SHORT=0 keeps LB_MSM_T)
-  const bool msm_short = use_msm && lone && n_sets <= ctx->msm_short_max && ctx->msm_short;
-  const uint32_t msm_T = msm_short ? ctx->msm_t_lone : LB_MSM_T;
-  const size_t max_chunks = use_msm ? n_ent / msm_T + LB_MSM_BUCKETS : 0;
-  uint32_t* d_mkeys = use_msm ? ws.take<uint32_t>(n_ent) : nullptr;
-  uint32_t* d_msorted = use_msm ? ws.take<uint32_t>(n_ent) : nullptr;
-  uint32_t* d_mhist = use_msm ? ws.take<uint32_t>(4 * (LB_MSM_BUCKETS + 1)) : nullptr;
-  g2j* d_mcsum = use_msm ? ws.take<g2j>(max_chunks) : nullptr;
-  g2j* d_mbsum = use_msm ? ws.take<g2j>(LB_MSM_BUCKETS) : nullptr;
-  g2j* d_mG = use_msm ? ws.take<g2j>(LB_MSM_POS) : nullptr;
-  // steps organisation: size histogram + cursors, gt, row offsets, order, meta, G, level products
-  uint32_t* d_rhist = steps ? ws.take<uint32_t>(2 * ((size_t)ns + 1)) : nullptr;
-  uint32_t* d_rgt = steps ? ws.take<uint32_t>((size_t)ns + 1) : nullptr;
-  uint32_t* d_rowoff = steps ? ws.take<uint32_t>((size_t)ns + 1) : nullptr;
-  uint32_t* d_rpos = steps ? ws.take<uint32_t>(n_req) : nullptr;
-  uint32_t* d_rinv = steps ? ws.take<uint32_t>(n_req) : nullptr;
-  uint32_t* d_rmeta = steps ? ws.take<uint32_t>(1) : nullptr;
-  // a lone mid-size call splits every lane of the step-major accumulation (its time is the
-  // one-lane latency of a lane's 68 lines: 17 or 34 lines a lane instead; LB_STEP_SPLIT forces)
-  uint32_t lsplit = 1;
-  if (steps) {
-    lsplit = lone ? step_split_for(n_sets) : 1u;
-    if (ctx->step_split) lsplit = ctx->step_split;
+  LB_STAGE("step_acc", 0, step_acc_kernel(p), blocks_for(n_sets * lsplit), TPB, n_sets, n_pairs, b.rows, b.req_off,
+           (const uint32_t*)b.lines, b.G);
+  if (!p.merged) {
+    LB_STAGE("req_horner", 0, k_req_horner, n_req * lsplit, TPB, n_req, n_sets, b.rows, b.req_off, (const uint32_t*)b.G,
+             (const uint8_t*)b.bad, lsplit > 1 ? b.Fparts : b.F, (const uint8_t*)nullptr);
+    if (lsplit > 1)
+      LB_STAGE("req_horner", 0, k_req_join, n_req, TPB, n_req, lsplit, (const fp12*)b.Fparts, (const uint8_t*)b.bad,
+               b.F, (const uint8_t*)nullptr);
+    return LB_OK;
   }
-  uint32_t* d_G = steps ? ws.take<uint32_t>(144 * (size_t)ns * lsplit) : nullptr;
-  fp12* d_Fparts = steps && lsplit > 1 ? ws.take<fp12>((size_t)(n_req ? n_req : 1) * lsplit) : nullptr;
-  // a lone mid-size call's signature decode as round programs (k_sm_dec_prep / k_lp_dec / k_sm_dec_finish)
-  const bool dec_lp = lone && !d_sig_pre && n_sets && n_sets <= ctx->lp_dec_max && ctx->lp_decode;
-  uint32_t* d_dec_in = dec_lp ? ws.take<uint32_t>((size_t)ns * 4 * 16) : nullptr;
-  uint32_t* d_dec_fl = dec_lp ? ws.take<uint32_t>((size_t)ns * 3) : nullptr;
-  uint32_t* d_dec_out = dec_lp ? ws.take<uint32_t>((size_t)ns * 2 * 16) : nullptr;
-  uint32_t* d_dec_ofl = dec_lp ? ws.take<uint32_t>((size_t)ns * 2) : nullptr;
-  uint8_t* d_dec_pre = dec_lp ? ws.take<uint8_t>(ns) : nullptr;
-  if (dec_lp) LB_TRY(lp_ensure(ctx));
-  // ... and, up to LB_LP_HF_MAX sets, its hash finish (k_hf_prep / k_lp_hf / k_hf_finish; above that
-  // the workgroups queue: 1,536 / 2,048 sets 13.4 -> 11.0 / 11.8 ms, 4,704 (C5) 16.1 -> 17.4,
-  // profiles/r06/orgs_probe_r06hf.json; LB_LP_HASH_FINISH=0: k_hash_finish)
-  const bool hf_lp = lone && n_sets && n_sets <= ctx->lp_hf_max && ctx->lp_hash_finish;
-  uint32_t* d_hf_in = hf_lp ? ws.take<uint32_t>((size_t)ns * 12 * 16) : nullptr;
-  uint32_t* d_hf_out = hf_lp ? ws.take<uint32_t>((size_t)ns * 6 * 16) : nullptr;
-  if (hf_lp) LB_TRY(lp_ensure(ctx));
-  // ... and, up to LB_LP_LINES_MAX sets of the steps organisation, its lines (k_lines_prep /
-  // k_lp_lines / k_lines_store; LB_LP_LINES=0: k_lines_rows)
-  const bool lines_lp = steps && lone && n_sets <= ctx->lp_lines_max && ctx->lp_lines;
-  uint32_t* d_ll_in = lines_lp ? ws.take<uint32_t>((size_t)ns * 9 * 16) : nullptr;
-  uint32_t* d_ll_out = lines_lp ? ws.take<uint32_t>((size_t)ns * LB_LP_LINES_NOUT * 16) : nullptr;
-  if (lines_lp) LB_TRY(lp_ensure(ctx));
-  fp12* d_Pl = steps ? ws.take<fp12>(63) : nullptr;
-  // the level products' two stages (k_level_part's partials, the first k_level_wc pass's output)
-  const bool level_wc = steps && merged && ctx->level_wc;
-  const uint32_t lvl_per = level_wc ? level_blocks(n_sets * lsplit, n_req, lone) * 256u : 0u;
-  fp12* d_lvA = level_wc ? ws.take<fp12>(63 * (size_t)lvl_per) : nullptr;
-  fp12* d_lvB = level_wc ? ws.take<fp12>(63 * (size_t)((lvl_per + LB_LVL_GROUP - 1) / LB_LVL_GROUP)) : nullptr;
-  uint8_t* d_lhA = level_wc ? ws.take<uint8_t>(63 * (size_t)lvl_per) : nullptr;
-  uint8_t* d_lhB = level_wc ? ws.take<uint8_t>(63 * (size_t)lvl_per) : nullptr;
-  uint32_t* d_mt_in = mtail ? ws.take<uint32_t>((size_t)LB_MTAIL_NIN * 16) : nullptr;
-  uint32_t* d_mt_out = mtail && partial ? ws.take<uint32_t>(12 * 16) : nullptr;
-  uint32_t* d_mb_in0 = bits_lp ? ws.take<uint32_t>((size_t)LB_MSM_BITS_INST * LB_MSM_BITS_GROUP * 6 * 16) : nullptr;
-  uint32_t* d_mb_in1 = bits_lp ? ws.take<uint32_t>((size_t)LB_MSM_BITS_INST * 6 * 16) : nullptr;
-  uint32_t* d_mb_in2 = bits_lp ? ws.take<uint32_t>((size_t)LB_MSM_BITS_INST / 8 * 6 * 16) : nullptr;
-  const Rows rows{d_rowoff, d_rinv, d_rpos, d_rmeta, lsplit};
-  sl.h_stats[0] = sl.h_stats[1] = 0;
-  if (ws.off > ws.cap) {
-    ctx->err = "workspace overflow";
-    return LB_ERR_OUT_OF_MEMORY;
-  }
-  LB_TRY(stream_wait(ctx, sl, 0, 1, 0));
-  if (n_sets) {
-    if (hf_lp && n_sets <= ctx->lp_hash_full) {  // (the whole curve part as one program per set, k_lp_hash)
-      LB_STAGE("hash_finish", 1, k_hu_prep, blocks_for(n_sets, 256), 256u, n_sets, d_msgs, d_hf_in);
-      LB_STAGE("hash_finish", 1, k_lp_hash, n_sets, LB_LP_NARROW_ROWS * 16u,
-               ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_HASH_FULL].off, n_sets, (const uint32_t*)d_hf_in, d_hf_out);
-      LB_STAGE("hash_finish", 1, k_hf_finish, blocks_for(n_sets * 6u, 256), 256u, n_sets, (const uint32_t*)d_hf_out,
-               d_h);
-    } else {
-      LB_STAGE("hash_half", 1, k_hash_half, blocks_for(2 * n_sets), TPB, n_sets, d_msgs, d_q);
-      if (hf_lp) {  // (a lone mid-size call: clear_cofactor(Q0 + Q1) as round programs, k_lp_hf)
-        LB_STAGE("hash_finish", 1, k_hf_prep, blocks_for(n_sets * 12u, 256), 256u, n_sets, (const g2j*)d_q, d_hf_in);
-        const bool nar = ctx->lp_narrow & 1u;
-        LB_STAGE("hash_finish", 1, k_lp_hf, n_sets, (nar ? LB_LP_NARROW_ROWS : LB_LP_HF_ROWS) * 16u,
-                 ctx->d_lp + LB_LP_PROGS[nar ? LB_LP_PROG_HASH_FINISH_NARROW : LB_LP_PROG_HASH_FINISH].off, n_sets,
-                 (const uint32_t*)d_hf_in, d_hf_out);
-        LB_STAGE("hash_finish", 1, k_hf_finish, blocks_for(n_sets * 6u, 256), 256u, n_sets, (const uint32_t*)d_hf_out,
-                 d_h);
-      } else {
-        LB_STAGE("hash_finish", 1, k_hash_finish, blocks_for(n_sets), TPB, n_sets, d_q, d_h);
-      }
+  // (mtail: the merged pair's Miller value comes from the round program, not as lines)
+  const uint32_t s_pair = p.mtail ? 0xffffffffu : n_sets + n_req;
+  if (p.level_wc) {
+    const dim3 g_part(p.lvl_per / 256u, 63);
+    LB_STAGE("level_prod", 0, k_level_part, g_part, 256u, n_req, n_sets, b.rows, b.req_off, (const uint32_t*)b.G,
+             (const uint8_t*)b.bad, p.lvl_per, b.lvA, b.lhA);
+    uint32_t pin = p.lvl_per;
+    fp12 *src = b.lvA, *dst = b.lvB;
+    uint8_t *sh = b.lhA, *dh = b.lhB;
+    for (;;) {
+      const uint32_t pout = (pin + LB_LVL_GROUP - 1) / LB_LVL_GROUP;
+      const dim3 g_wc(pout, 63);
+      LB_STAGE("level_wc", 0, k_level_wc, g_wc, TPB, pin, (const fp12*)src, (const uint8_t*)sh, pout, dst, dh, n_pairs,
+               s_pair, (const uint32_t*)b.lines, pout == 1 ? b.Pl : (fp12*)nullptr);
+      if (pout == 1) break;
+      pin = pout;
+      std::swap(src, dst);
+      std::swap(sh, dh);
     }
-  }
-  LB_STAGE("req_flags", 0, k_req_flags, blocks_for(n_req), TPB, n_req, d_req_off, d_single);
-  if (steps) {  // size-descending order and row offsets (before stream 1's lines)
-    uint32_t* d_rcur = d_rhist + (ns + 1);
-    LB_HIP(hipMemsetAsync(d_rhist, 0, 2 * ((size_t)ns + 1) * sizeof(uint32_t), sl.st[0]));
-    hipLaunchKernelGGL(k_rows_hist, dim3(blocks_for(n_req, 256)), dim3(256), 0, sl.st[0], n_req, d_req_off, d_rhist);
-    LB_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, sl.st[0], n_sets, (const uint32_t*)d_rhist, d_rgt, d_rowoff,
-                       d_rmeta);
-    LB_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rows_pos, dim3(blocks_for(n_req, 256)), dim3(256), 0, sl.st[0], n_req, d_req_off,
-                       (const uint32_t*)d_rgt, d_rcur, d_rpos, d_rinv);
-    LB_HIP(hipGetLastError());
-  }
-  if (n_sets) {
-    const PkSource src{d_pks, d_pk_idx, ctx->d_table, ctx->table_n};
-    LB_STAGE("pubkeys", 0, k_pubkeys_single, blocks_for(n_sets), TPB, n_sets, src, d_pk_off, d_pk, d_pk_st);
-    if (d_pk_off)
-      // one wave per set, grid-stride: enough waves that every aggregate of a
-      // C4/C5-sized call (thousands of committee sets) gets its own
-      LB_STAGE("pubkeys_agg", 0, k_pubkeys_agg, n_sets < 16384u ? n_sets : 16384u, TPB, n_sets, src, d_pk_off, d_pk,
-               d_pk_st);
-    LB_STAGE("scalar_pk", 0, k_scalar_pk, blocks_for(n_sets), TPB, n_sets, d_seed, (const g1j*)d_pk,
-             (const uint8_t*)d_single, d_pk_st, d_rpk);
-  }
-  LB_TRY(stream_wait(ctx, sl, 0, 1, 1));
-  if (steps && lines_lp) {
-    // (a lone mid-size call: each slot's 68 lines as a round program, k_lp_lines)
-    LB_STAGE("lines", 1, k_lines_prep, blocks_for(n_sets * 9u, 256), 256u, n_sets, rows, d_req_off, (const g1j*)d_rpk,
-             (const g2j*)d_h, d_ll_in);
-    LB_STAGE("lines", 1, k_lp_lines, n_sets, LB_LP_HF_ROWS * 16u, ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_LINES].off, n_sets,
-             (const uint32_t*)d_ll_in, d_ll_out);
-    LB_STAGE("lines", 1, k_lines_store, (uint32_t)(((size_t)n_sets * LB_MILLER_LINES * 72 + 255) / 256), 256u, n_sets,
-             n_pairs, (const uint32_t*)d_ll_out, d_lines);
-  } else if (steps) {
-    if (ctx->lines_waves == 1)
-      LB_STAGE("lines", 1, k_lines_rows<1>, blocks_for(n_sets), TPB, n_sets, n_pairs, rows, d_req_off,
-               (const g1j*)d_rpk, d_h, d_lines);
-    else
-      LB_STAGE("lines", 1, k_lines_rows<2>, blocks_for(n_sets), TPB, n_sets, n_pairs, rows, d_req_off,
-               (const g1j*)d_rpk, d_h, d_lines);
-  } else if (n_sets && (by_lines || by_wave)) {
-    // (small calls are latency-bound: the spill-free one-wave build unless LB_LINES_WAVES=2)
-    if (ctx->lines_waves_small == 1)
-      LB_STAGE("lines", 1, k_lines<1>, blocks_for(n_sets), TPB, n_sets, n_pairs, 0u, (const g1j*)d_rpk,
-               (const g2j*)d_h, d_lines);
-    else
-      LB_STAGE("lines", 1, k_lines<2>, blocks_for(n_sets), TPB, n_sets, n_pairs, 0u, (const g1j*)d_rpk,
-               (const g2j*)d_h, d_lines);
-  }
-  if (n_sets && by_wave)
-    LB_STAGE("miller_wave", 1, k_pair_wc, n_sets, TPB, n_sets, n_pairs, (const uint32_t*)d_lines, d_f);
-  else if (n_sets && !by_lines)
-    LB_STAGE("miller_sets", 1, k_miller_sets, blocks_for(n_sets), TPB, n_sets, (const g1j*)d_rpk, (const g2j*)d_h,
-             d_f);
-  if (n_sets) {
-    if (!d_sig_pre && dec_lp) {
-      // (a lone mid-size call: the signatures' decode as round programs, k_lp_dec -- its one-lane
-      // chain is ~5.7 ms whatever the count below the GPU's width)
-      LB_STAGE("decode_sigs", 0, k_sm_dec_prep, blocks_for(n_sets, 256), 256u, n_sets, d_sigs, d_sig_off, d_dec_in,
-               d_dec_fl, d_dec_pre);
-      LB_STAGE("decode_sigs", 0, k_lp_dec, n_sets, LB_LP_DEC_ROWS * 16u,
-               ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_SIG_DECODE].off, n_sets, (const uint32_t*)d_dec_in,
-               (const uint32_t*)d_dec_fl, d_dec_out, d_dec_ofl);
-      LB_STAGE("decode_sigs", 0, k_sm_dec_finish, blocks_for(n_sets, 256), 256u, n_sets, (const uint8_t*)d_dec_pre,
-               (const uint32_t*)d_dec_in, (const uint32_t*)d_dec_fl, (const uint32_t*)d_dec_out,
-               (const uint32_t*)d_dec_ofl, d_sig, d_sig_st, (const uint8_t*)d_single);
-    } else if (!d_sig_pre) {
-      LB_STAGE("decode_sigs", 0, k_decode_sigs, blocks_for(n_sets), TPB, n_sets, d_sigs, d_sig_off,
-               (const uint8_t*)d_single, d_sig, d_sig_st);
-    }
-    if (!use_msm)
-      LB_STAGE("scalar_sig", 0, k_scalar_sig, blocks_for(n_sets), TPB, n_sets, d_seed, (const g2j*)d_sig,
-               (const uint8_t*)d_sig_st, d_rsig, (const uint8_t*)nullptr);
-  }
-  if (steps)  // request status (k_miller_acc's side reduction in the pairs organisation)
-    LB_STAGE("req_status", 0, k_req_status, n_req < 4096u ? n_req : 4096u, TPB, n_req, d_req_off,
-             (const uint8_t*)d_sig_st, (const uint8_t*)d_pk_st, d_bad, d_req_err);
-  if (use_msm) {
-    // S_all = sum r_i sig_i over the good requests' sets: one bucket MSM (k_msm.hip)
-    uint32_t* d_off = d_mhist + (LB_MSM_BUCKETS + 1);
-    uint32_t* d_coff = d_off + (LB_MSM_BUCKETS + 1);
-    uint32_t* d_cur = d_coff + (LB_MSM_BUCKETS + 1);
-    LB_HIP(hipMemsetAsync(d_mhist, 0, (LB_MSM_BUCKETS + 1) * sizeof(uint32_t), sl.st[0]));
-    LB_STAGE("msm_digits", 0, k_msm_scalars, n_req, TPB, n_req, d_req_off, d_seed, (const uint64_t*)nullptr,
-             (const g2j*)d_sig, (const uint8_t*)d_sig_st, (const uint8_t*)d_pk_st, d_mkeys, d_mhist);
-    hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(1024), 0, sl.st[0], (const uint32_t*)d_mhist, d_off, d_coff, d_cur,
-                       msm_T);
-    LB_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_msm_scatter, dim3(blocks_for((uint32_t)n_ent, 256)), dim3(256), 0, sl.st[0], (uint32_t)n_ent,
-                       (const uint32_t*)d_mkeys, (const uint32_t*)d_off, d_cur, d_msorted);
-    LB_HIP(hipGetLastError());
-    LB_STAGE("msm_chunks", 0, k_msm_chunks, blocks_for((uint32_t)max_chunks), TPB, (uint32_t)max_chunks,
-             (const uint32_t*)d_off, (const uint32_t*)d_coff, (const uint32_t*)d_msorted, (const g2j*)d_sig, d_mcsum,
-             msm_T);
-    const uint32_t bl = msm_wide ? LB_MSM_BLANES : 1u;
-    LB_STAGE("msm_buckets", 0, k_msm_buckets, blocks_for(LB_MSM_BUCKETS * bl), TPB, (const uint32_t*)d_coff,
-             (const g2j*)d_mcsum, d_mbsum, bl);
-    if (bits_lp) {
-      // (a lone call's bit sums as three levels of round programs, 8:1 each; the last writes the
-      // 33 G_p into the merged-check program's input records, so k_mtail_prep skips them)
-      LB_STAGE("msm_bits", 0, k_msm_bits_prep, blocks_for(LB_MSM_BITS_INST * LB_MSM_BITS_GROUP * 6u, 256), 256u,
-               (const g2j*)d_mbsum, d_mb_in0);
-      constexpr uint32_t NI = LB_MSM_BITS_GROUP * 6u;
-      LB_STAGE("msm_bits", 0, k_lp_msm_bits, LB_MSM_BITS_INST, LB_LP_TPB, ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_MSM_BITS0].off,
-               (uint32_t)LB_MSM_BITS_INST, NI, 6u, (const uint32_t*)d_mb_in0, d_mb_in1);
-      LB_STAGE("msm_bits", 0, k_lp_msm_bits, LB_MSM_BITS_INST / 8u, LB_LP_TPB,
-               ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_MSM_BITS1].off, (uint32_t)LB_MSM_BITS_INST / 8u, NI, 6u,
-               (const uint32_t*)d_mb_in1, d_mb_in2);
-      LB_STAGE("msm_bits", 0, k_lp_msm_bits, LB_MSM_POS, LB_LP_TPB, ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_MSM_BITS2].off,
-               (uint32_t)LB_MSM_POS, NI, 6u, (const uint32_t*)d_mb_in2, d_mt_in + (size_t)12 * LB_MTAIL_LEVELS * 16);
-    } else {
-      if (msm_wide)
-        LB_STAGE("msm_bits", 0, k_msm_bits<LB_MSM_BITS_TPB>, LB_MSM_POS, LB_MSM_BITS_TPB, (const g2j*)d_mbsum, d_mG);
-      else
-        LB_STAGE("msm_bits", 0, k_msm_bits<TPB>, LB_MSM_POS, TPB, (const g2j*)d_mbsum, d_mG);
-    }
-    if (!mtail) LB_STAGE("msm_final", 0, k_msm_final, 1u, TPB, (const g2j*)d_mG, d_Sall);
-    if (!fold && !mtail)
-      LB_STAGE("lines_all", 0, k_lines_S, 1u, TPB, 1u, n_pairs, n_sets + n_req, (const g2a*)d_Sall, d_lines,
-               (const uint8_t*)nullptr);
   } else {
-    LB_STAGE("sum_tree", 0, k_sum_tree, n_req, TPB, n_req, d_req_off, (const g2j*)d_rsig, d_S, (const uint8_t*)nullptr);
-    if (steps && merged) {  // S_all of the good requests and its lines, ahead of the level products
-      LB_STAGE("merge", 0, k_merge, 1u, TPB, n_req, (const g2a*)d_S, (const fp12*)nullptr, (const uint8_t*)d_bad, d_Sall,
-               (fp12*)nullptr, (const fp12*)nullptr);
-      LB_STAGE("lines_all", 0, k_lines_S, 1u, TPB, 1u, n_pairs, n_sets + n_req, (const g2a*)d_Sall, d_lines,
-               (const uint8_t*)nullptr);
+    LB_STAGE("level_prod", 0, k_level_prod, 63u, 256u, n_req, n_sets, n_pairs, s_pair, b.rows, b.req_off,
+             (const uint32_t*)b.G, (const uint8_t*)b.bad, (const uint32_t*)b.lines, b.Pl);
+  }
+  // (mtail: the round program runs the Horner chain over the level products itself, on the
+  // Miller loop's squarings of (-g1, S_all): no one-wave k_horner_all)
+  if (!p.mtail) LB_STAGE("horner_all", 0, k_horner_all, 1u, TPB, (const fp12*)b.Pl, b.Fall);
+  return LB_OK;
+}
+
+// pairs organisation: several pairs per lane sharing the Fp12 squarings, the requests whole or
+// in halves (k_split_requests / k_join_halves), the merged pair folded in as one more workgroup
+static int enqueue_acc_pairs(lb_ctx* ctx, Slot& sl, const PipePlan& p, const PipeBufs& b) {
+  const uint32_t n_req = p.n_req, n_pairs = p.n_pairs;
+  const fp12* fS_in = p.tail_wave ? nullptr : (const fp12*)b.fS;
+  if (p.split)
+    LB_ENQUEUE(sl.st[0], k_split_requests, blocks_for(n_req + 1), TPB, n_req, b.req_off, b.off2);
+  const uint32_t nr = p.split ? 2 * n_req : n_req;
+  const uint32_t rpw = TPB / p.acc_lpr, grid = (nr + rpw - 1) / rpw + (p.fold ? 1u : 0u);
+  LB_STAGE("miller_acc", 0, miller_acc_kernel(p), grid, TPB, nr, p.split ? (const uint32_t*)b.off2 : b.req_off, n_pairs,
+           (const uint32_t*)b.lines, p.split ? (const fp12*)nullptr : fS_in, (const uint8_t*)b.sig_st,
+           (const uint8_t*)b.pk_st, p.split ? b.acc_F : b.F, p.split ? b.acc_bad : b.bad,
+           p.split ? b.acc_err : b.req_err, p.split ? 1u : 0u, p.fold ? (const g2a*)b.Sall : (const g2a*)nullptr, b.Fx);
+  if (p.split)
+    LB_STAGE("join_halves", 0, k_join_halves, blocks_for(n_req), TPB, n_req, b.req_off, (const fp12*)b.acc_F,
+             (const uint8_t*)b.acc_bad, (const uint8_t*)b.acc_err, fS_in, b.F, b.bad, b.req_err);
+  return LB_OK;
+}
+
+// the per-request products F_k (or, steps + merged, the call's level products)
+static int enqueue_accumulate(lb_ctx* ctx, Slot& sl, const PipePlan& p, const PipeBufs& b) {
+  if (p.steps) return enqueue_acc_steps(ctx, sl, p, b);
+  if (p.by_lines) return enqueue_acc_pairs(ctx, sl, p, b);
+  LB_STAGE("prod_tree", 0, k_prod_tree, p.n_req, TPB, p.n_req, b.req_off, (const fp12*)b.f,
+           p.tail_wave ? (const fp12*)nullptr : (const fp12*)b.fS, (const uint8_t*)b.sig_st, (const uint8_t*)b.pk_st, b.F,
+           b.bad, b.req_err);
+  return LB_OK;
+}
+
+// Merged check: one tail for the whole call; per-request tails only if it fails.  A two-phase
+// call stops at the merged Miller product instead.  On b.ts: the slot's stream 0, or with
+// LB_TAIL_PRIO=1 a shared high-priority stream (measured slower, off by default).
+// *tails: whether the per-request tails follow now (not for a two-phase call that holds its slot)
+static int enqueue_merged(lb_ctx* ctx, Slot& sl, const PipePlan& p, const PipeBufs& b, bool* tails) {
+  const uint32_t n_req = p.n_req, n_sets = p.n_sets, n_pairs = p.n_pairs;
+  const hipStream_t ts = b.ts;
+  *tails = true;
+  if (ts != sl.st[0]) {
+    LB_HIP(hipEventRecord(sl.dep[3], sl.st[0]));
+    LB_HIP(hipStreamWaitEvent(ts, sl.dep[3], 0));
+  }
+  LB_HIP(hipMemsetAsync(b.mflag, 0, 2, ts));
+  if (!p.steps) {  // (steps: F_all from the level products and the Horner chain, S_all's lines included)
+    LB_STAGE_ON("merge", ts, k_merge, 1u, TPB, n_req, p.use_msm ? (const g2a*)nullptr : (const g2a*)b.S,
+                (const fp12*)b.F, (const uint8_t*)b.bad, b.Sall, b.Fall, (const fp12*)b.Fx);
+    if (!p.use_msm)  // (with the MSM: folded into k_miller_acc, or stored right after the MSM)
+      LB_STAGE_ON("lines_all", ts, k_lines_S, 1u, TPB, 1u, n_pairs, n_sets + n_req, (const g2a*)b.Sall, b.lines,
+                  (const uint8_t*)nullptr);
+  }
+  const uint32_t* merged_lines = (p.fold || p.steps) ? nullptr : (const uint32_t*)b.lines;
+  const uint32_t mt_tpb = p.mt_wide ? LB_LP_MTAIL_ROWS * 16u : (uint32_t)LB_LP_TPB;
+  if (p.mtail) {
+    LB_ENQUEUE(ts, k_mtail_prep, 1, 256, (const fp12*)b.Pl, p.bits_lp ? (const g2j*)nullptr : (const g2j*)b.mG, b.mt_in);
+    if (p.partial) {  // F_all * Miller(-g1, S_all) back into Fall, encoded by k_partial below
+      LB_STAGE_ON("mtail", ts, k_lp_mtail, 1u, mt_tpb,
+                  lp_prog(ctx, p.mt_wide ? LB_LP_PROG_MTAIL_PARTIAL_WIDE : LB_LP_PROG_MTAIL_PARTIAL),
+                  (const uint32_t*)b.mt_in, (uint8_t*)nullptr, b.mt_out);
+      LB_ENQUEUE(ts, k_records_to_fp12, 1, 64, (const uint32_t*)b.mt_out, b.Fall);
     }
   }
-  if (tail_wave && !merged)
-    LB_STAGE("lines_S", 0, k_lines_S, blocks_for(n_req), TPB, n_req, n_pairs, n_sets, (const g2a*)d_S, d_lines,
-             (const uint8_t*)nullptr);
-  else if (!tail_wave)
-    LB_STAGE("miller_S", 0, k_miller_S, blocks_for(n_req), TPB, n_req, (const g2a*)d_S, d_fS);
-  const fp12* fS_in = tail_wave ? nullptr : (const fp12*)d_fS;
-  LB_TRY(stream_wait(ctx, sl, 1, 0, 2));
-  fp12* d_Fx = fold ? ws.take<fp12>(1) : nullptr;
-  if (ws.off > ws.cap) {
+  if (p.partial) {
+    // two-phase call: the merged Miller product goes to the host, which
+    // combines it with the other GPUs' partials; the tails wait for its verdict
+    LB_STAGE_ON("partial", ts, k_partial, 1u, TPB, n_pairs, n_sets + n_req, merged_lines, (const fp12*)b.Fall,
+                b.partial);
+    LB_HIP(hipMemcpyAsync(sl.h_partial, b.partial, LB_GT_BYTES, hipMemcpyDeviceToHost, ts));
+    LB_HIP(hipEventRecord(sl.partial_ev, ts));
+  } else if (p.mtail) {
+    LB_STAGE_ON("mtail", ts, k_lp_mtail, 1u, mt_tpb,
+                lp_prog(ctx, p.mt_wide ? LB_LP_PROG_MTAIL_CHECK_WIDE : LB_LP_PROG_MTAIL_CHECK), (const uint32_t*)b.mt_in,
+                b.mflag, (uint32_t*)nullptr);
+  } else {
+    LB_STAGE_ON("tail_all", ts, k_tail, 1u, TPB, 1u, n_pairs, n_sets + n_req, merged_lines, (const fp12*)b.Fall,
+                (const uint8_t*)(b.mflag + 1), b.mflag, (const uint8_t*)nullptr);
+  }
+  if (ts != sl.st[0]) {
+    LB_HIP(hipEventRecord(sl.dep[4], ts));
+    LB_HIP(hipStreamWaitEvent(sl.st[0], sl.dep[4], 0));
+  }
+  if (p.partial) {
+    if (p.tp_release) {
+      // the call completes on its own as if the combined check passed (every request not
+      // already false valid: no per-request work) and frees its slot at once; a failed
+      // combined check re-verifies the shard as a one-phase call (lb_verify_requests_finish)
+      LB_HIP(hipMemsetAsync(b.mflag, 1, 1, sl.st[0]));
+    } else {
+      sl.partial_pending = true;
+      *tails = false;
+    }
+  }
+  return LB_OK;
+}
+
+// what the tails need of a call (run_tails, now or after lb_verify_requests_finish)
+static void fill_state(PipeState& ps, const PipePlan& p, const PipeBufs& b) {
+  ps.n_req = p.n_req;
+  ps.n_sets = p.n_sets;
+  ps.n_pairs = p.n_pairs;
+  ps.merged = p.merged;
+  ps.tail_wave = p.tail_wave;
+  ps.msm = p.use_msm;
+  ps.d_seed = b.seed;
+  ps.d_sig = b.sig;
+  ps.d_sig_st = b.sig_st;
+  ps.d_rsig = b.rsig;
+  ps.d_req_off = b.req_off;
+  ps.d_lines = b.lines;
+  ps.d_S = b.S;
+  ps.d_F = b.F;
+  ps.d_rt_in = b.rt_in;
+  ps.d_rt_fl = b.rt_fl;
+  ps.d_bad = b.bad;
+  ps.d_valid = b.valid;
+  ps.d_mflag = b.mflag;
+  ps.d_mstats = b.mstats;
+  ps.steps = p.steps;
+  ps.rows = b.rows;
+  ps.d_G = b.G;
+  ps.d_Fparts = b.Fparts;
+}
+
+// Core pipeline on device-resident inputs (all pointers are device pointers): plan the call
+// (bls_plan.h), lay its workspace out, check the slab once, then enqueue the stages as a
+// two-stream DAG inside the slot:
+//   0: flags, row order -> pubkeys -> r_i pk_i -> [ev 1] -> decode sigs -> request status ->
+//      S_all (bucket MSM) or S_k (ladders + tree) -> [wait 1] -> accumulation of the stored
+//      lines (step-major lanes, level products) -> merged check -> per-request tails
+//   1: hash_to_G2 -> [wait ev 1] -> lines of (r_i pk_i, H_i)
+// d_sig_pre / d_sst_pre: signatures already decoded and validated (same-message
+// phase 2): no decode, d_sigs / d_sig_off unused
+int run_pipeline(lb_ctx* ctx, Slot& sl, uint32_t n_req, uint32_t n_sets, const uint32_t* d_req_off,
+                 const uint8_t* d_pks, const uint32_t* d_pk_off, const uint32_t* d_pk_idx, const uint8_t* d_msgs, const uint8_t* d_sigs,
+                 const uint32_t* d_sig_off, const uint8_t* d_seed, uint8_t* d_valid, uint8_t* d_req_err,
+                 uint8_t* d_set_status, Bump& ws, bool partial = false, const g2j* d_sig_pre = nullptr,
+                 const uint8_t* d_sst_pre = nullptr) {
+  PipeShape shape;
+  shape.n_req = n_req;
+  shape.n_sets = n_sets;
+  shape.lone = call_is_lone(ctx, sl);
+  shape.partial = partial;
+  shape.presigned = d_sig_pre != nullptr;
+  shape.prio_slot = &sl == &ctx->prio();
+  const PipePlan plan = plan_pipeline(ctx->cfg, shape);
+  sl.h_stats[0] = sl.h_stats[1] = 0;
+  if (plan.latency_path)
+    return run_lp(ctx, sl, n_req, n_sets, d_req_off, d_pks, d_pk_off, d_pk_idx, d_msgs, d_sigs, d_sig_off, d_seed,
+                  d_valid, d_req_err, d_set_status, ws);
+  const PipeLayout lay = layout_pipeline(plan, ws.off);
+  if (ws.off + lay.bytes > ws.cap) {  // (the one capacity check: nothing is enqueued yet)
     ctx->err = "workspace overflow";
     return LB_ERR_OUT_OF_MEMORY;
   }
-  if (steps) {
-#define LB_STEP_STAGE(M, W)                                                                               \
-  LB_STAGE("step_acc", 0, (k_step_acc<M, W>), blocks_for(n_sets * lsplit), TPB, n_sets, n_pairs, rows, d_req_off, \
-           (const uint32_t*)d_lines, d_G)
-    if (ctx->step_mode == 1)
-      LB_STEP_STAGE(1, 1);
-    else if (ctx->step_mode == 2 && ctx->step_waves == 2)
-      LB_STEP_STAGE(2, 2);
-    else if (ctx->step_mode == 2)
-      LB_STEP_STAGE(2, 1);
-    else if (ctx->step_waves == 2)
-      LB_STEP_STAGE(0, 2);
-    else
-      LB_STEP_STAGE(0, 1);
-#undef LB_STEP_STAGE
-    if (merged) {
-      // (mtail: the merged pair's Miller value comes from the round program, not as lines)
-      const uint32_t s_pair = mtail ? 0xffffffffu : n_sets + n_req;
-      if (level_wc) {
-        const dim3 g_part(lvl_per / 256u, 63);
-        LB_STAGE("level_prod", 0, k_level_part, g_part, 256u, n_req, n_sets, rows, d_req_off, (const uint32_t*)d_G,
-                 (const uint8_t*)d_bad, lvl_per, d_lvA, d_lhA);
-        uint32_t pin = lvl_per;
-        fp12 *src = d_lvA, *dst = d_lvB;
-        uint8_t *sh = d_lhA, *dh = d_lhB;
-        for (;;) {
-          const uint32_t pout = (pin + LB_LVL_GROUP - 1) / LB_LVL_GROUP;
-          const dim3 g_wc(pout, 63);
-          LB_STAGE("level_wc", 0, k_level_wc, g_wc, TPB, pin, (const fp12*)src, (const uint8_t*)sh, pout, dst, dh,
-                   n_pairs, s_pair, (const uint32_t*)d_lines, pout == 1 ? d_Pl : (fp12*)nullptr);
-          if (pout == 1) break;
-          pin = pout;
-          std::swap(src, dst);
-          std::swap(sh, dh);
-        }
-      } else {
-        LB_STAGE("level_prod", 0, k_level_prod, 63u, 256u, n_req, n_sets, n_pairs, s_pair, rows, d_req_off,
-                 (const uint32_t*)d_G, (const uint8_t*)d_bad, (const uint32_t*)d_lines, d_Pl);
-      }
-      // (mtail: the round program runs the Horner chain over the level products itself, on the
-      // Miller loop's squarings of (-g1, S_all): no one-wave k_horner_all)
-      if (!mtail) LB_STAGE("horner_all", 0, k_horner_all, 1u, TPB, (const fp12*)d_Pl, d_Fall);
-    } else {
-      LB_STAGE("req_horner", 0, k_req_horner, n_req * lsplit, TPB, n_req, n_sets, rows, d_req_off,
-               (const uint32_t*)d_G, (const uint8_t*)d_bad, lsplit > 1 ? d_Fparts : d_F, (const uint8_t*)nullptr);
-      if (lsplit > 1)
-        LB_STAGE("req_horner", 0, k_req_join, n_req, TPB, n_req, lsplit, (const fp12*)d_Fparts, (const uint8_t*)d_bad,
-                 d_F, (const uint8_t*)nullptr);
-    }
-  } else if (by_lines) {
-    const uint32_t nr = split ? 2 * n_req : n_req;
-    const uint32_t* acc_off = d_req_off;
-    fp12* acc_F = d_F;
-    uint8_t* acc_bad = d_bad;
-    uint8_t* acc_err = d_req_err;
-    if (split) {
-      uint32_t* off2 = ws.take<uint32_t>(2 * (size_t)n_req + 1);
-      acc_F = ws.take<fp12>(2 * (size_t)n_req);
-      acc_bad = ws.take<uint8_t>(2 * (size_t)n_req);
-      acc_err = ws.take<uint8_t>(2 * (size_t)n_req);
-      if (ws.off > ws.cap) {
-        ctx->err = "workspace overflow";
-        return LB_ERR_OUT_OF_MEMORY;
-      }
-      hipLaunchKernelGGL(k_split_requests, dim3(blocks_for(n_req + 1)), dim3(TPB), 0, sl.st[0], n_req, d_req_off, off2);
-      LB_HIP(hipGetLastError());
-      acc_off = off2;
-    }
-    const uint32_t rpw = TPB / ctx->acc_lpr, grid = (nr + rpw - 1) / rpw + (fold ? 1u : 0u);
-    const fp12* acc_fS = split ? nullptr : fS_in;
-    const uint32_t halves = split ? 1u : 0u;
-#define LB_ACC_STAGE(L)                                                                                       \
-  LB_STAGE("miller_acc", 0, k_miller_acc<L>, grid, TPB, nr, acc_off, n_pairs, (const uint32_t*)d_lines, acc_fS, \
-           (const uint8_t*)d_sig_st, (const uint8_t*)d_pk_st, acc_F, acc_bad, acc_err, halves,               \
-           fold ? (const g2a*)d_Sall : (const g2a*)nullptr, d_Fx)
-    if (ctx->acc_lpr == 16)
-      LB_ACC_STAGE(16);
-    else if (ctx->acc_lpr == 32)
-      LB_ACC_STAGE(32);
-    else
-      LB_ACC_STAGE(64);
-#undef LB_ACC_STAGE
-    if (split)
-      LB_STAGE("join_halves", 0, k_join_halves, blocks_for(n_req), TPB, n_req, d_req_off, (const fp12*)acc_F,
-               (const uint8_t*)acc_bad, (const uint8_t*)acc_err, fS_in, d_F, d_bad, d_req_err);
-  } else
-    LB_STAGE("prod_tree", 0, k_prod_tree, n_req, TPB, n_req, d_req_off, (const fp12*)d_f, fS_in,
-             (const uint8_t*)d_sig_st, (const uint8_t*)d_pk_st, d_F, d_bad, d_req_err);
-  PipeState& ps = sl.ps;
-  ps.n_req = n_req;
-  ps.n_sets = n_sets;
-  ps.n_pairs = n_pairs;
-  ps.merged = merged;
-  ps.tail_wave = tail_wave;
-  ps.msm = use_msm;
-  ps.d_seed = d_seed;
-  ps.d_sig = d_sig;
-  ps.d_sig_st = d_sig_st;
-  ps.d_rsig = d_rsig;
-  ps.d_req_off = d_req_off;
-  ps.d_lines = d_lines;
-  ps.d_S = d_S;
-  ps.d_F = d_F;
-  ps.d_rt_in = d_rt_in;
-  ps.d_rt_fl = d_rt_fl;
-  ps.d_bad = d_bad;
-  ps.d_valid = d_valid;
-  ps.d_mflag = d_mflag;
-  ps.d_mstats = d_mstats;
-  ps.steps = steps;
-  ps.rows = rows;
-  ps.d_G = d_G;
-  ps.d_Fparts = d_Fparts;
-  if (merged) {
-    // merged check: one tail for the whole call; per-request tails only if it fails.
-    // LB_TAIL_PRIO=1 runs its chain of one-wave kernels on a shared high-priority
-    // stream instead of the slot's own (measured slower, off by default).
-    hipStream_t ts = sl.st[0];
-    if (ctx->tail_stream) {
-      ts = ctx->tail_stream;
-      LB_HIP(hipEventRecord(sl.dep[3], sl.st[0]));
-      LB_HIP(hipStreamWaitEvent(ts, sl.dep[3], 0));
-    }
-    LB_HIP(hipMemsetAsync(d_mflag, 0, 2, ts));
-    if (!steps) {  // (steps: F_all from the level products and the Horner chain, S_all's lines included)
-      LB_STAGE_ON("merge", ts, k_merge, 1u, TPB, n_req, use_msm ? (const g2a*)nullptr : (const g2a*)d_S,
-                  (const fp12*)d_F, (const uint8_t*)d_bad,
-                  d_Sall, d_Fall, (const fp12*)d_Fx);
-      if (!use_msm)  // (with the MSM: folded into k_miller_acc, or stored right after the MSM)
-        LB_STAGE_ON("lines_all", ts, k_lines_S, 1u, TPB, 1u, n_pairs, n_sets + n_req, (const g2a*)d_Sall, d_lines,
-                    (const uint8_t*)nullptr);
-    }
-    const uint32_t* merged_lines = (fold || steps) ? nullptr : (const uint32_t*)d_lines;
-    if (mtail) {
-      hipLaunchKernelGGL(k_mtail_prep, dim3(1), dim3(256), 0, ts, (const fp12*)d_Pl,
-                         bits_lp ? (const g2j*)nullptr : (const g2j*)d_mG, d_mt_in);
-      LB_HIP(hipGetLastError());
-      if (partial) {  // F_all * Miller(-g1, S_all) back into d_Fall, encoded by k_partial below
-        LB_STAGE_ON("mtail", ts, k_lp_mtail, 1u, mt_tpb, ctx->d_lp + LB_LP_PROGS[mt_wide ? LB_LP_PROG_MTAIL_PARTIAL_WIDE : LB_LP_PROG_MTAIL_PARTIAL].off,
-                    (const uint32_t*)d_mt_in, (uint8_t*)nullptr, d_mt_out);
-        hipLaunchKernelGGL(k_records_to_fp12, dim3(1), dim3(64), 0, ts, (const uint32_t*)d_mt_out, d_Fall);
-        LB_HIP(hipGetLastError());
-      }
-    }
-    if (partial) {
-      // two-phase call: the merged Miller product goes to the host, which
-      // combines it with the other GPUs' partials; the tails wait for its verdict
-      LB_STAGE_ON("partial", ts, k_partial, 1u, TPB, n_pairs, n_sets + n_req, merged_lines,
-                  (const fp12*)d_Fall, d_partial);
-      LB_HIP(hipMemcpyAsync(sl.h_partial, d_partial, LB_GT_BYTES, hipMemcpyDeviceToHost, ts));
-      LB_HIP(hipEventRecord(sl.partial_ev, ts));
-      if (ts != sl.st[0]) {
-        LB_HIP(hipEventRecord(sl.dep[4], ts));
-        LB_HIP(hipStreamWaitEvent(sl.st[0], sl.dep[4], 0));
-      }
-      if (ctx->tp_release) {
-        // the call completes on its own as if the combined check passed (every request not
-        // already false valid: no per-request work) and frees its slot at once; a failed
-        // combined check re-verifies the shard as a one-phase call (lb_verify_requests_finish)
-        LB_HIP(hipMemsetAsync(d_mflag, 1, 1, sl.st[0]));
-        return run_tails(ctx, sl);
-      }
-      sl.partial_pending = true;
-      return LB_OK;
-    }
-    if (mtail)
-      LB_STAGE_ON("mtail", ts, k_lp_mtail, 1u, mt_tpb, ctx->d_lp + LB_LP_PROGS[mt_wide ? LB_LP_PROG_MTAIL_CHECK_WIDE : LB_LP_PROG_MTAIL_CHECK].off,
-                  (const uint32_t*)d_mt_in, d_mflag, (uint32_t*)nullptr);
-    else
-      LB_STAGE_ON("tail_all", ts, k_tail, 1u, TPB, 1u, n_pairs, n_sets + n_req, merged_lines,
-                  (const fp12*)d_Fall, (const uint8_t*)(d_mflag + 1), d_mflag, (const uint8_t*)nullptr);
-    if (ts != sl.st[0]) {
-      LB_HIP(hipEventRecord(sl.dep[4], ts));
-      LB_HIP(hipStreamWaitEvent(sl.st[0], sl.dep[4], 0));
-    }
+  if (plan.needs_lp) LB_TRY(lp_ensure(ctx));
+  PipeBufs b{};
+  b.req_off = d_req_off;
+  b.pks = d_pks;
+  b.pk_off = d_pk_off;
+  b.pk_idx = d_pk_idx;
+  b.msgs = d_msgs;
+  b.sigs = d_sigs;
+  b.sig_off = d_sig_off;
+  b.seed = d_seed;
+  b.valid = d_valid;
+  b.req_err = d_req_err;
+  bind_workspace(b, ws.base, lay, plan.lsplit);
+  ws.off += lay.bytes;
+  if (d_sig_pre) b.sig = const_cast<g2j*>(d_sig_pre);
+  if (d_sst_pre)
+    b.sig_st = const_cast<uint8_t*>(d_sst_pre);
+  else if (d_set_status)
+    b.sig_st = d_set_status;
+  b.ts = plan.merged && ctx->tail_stream ? ctx->tail_stream : sl.st[0];
+
+  LB_TRY(stream_wait(ctx, sl, 0, 1, 0));
+  LB_TRY(enqueue_hash(ctx, sl, plan, b));
+  LB_TRY(enqueue_row_order(ctx, sl, plan, b));
+  LB_TRY(enqueue_pubkeys(ctx, sl, plan, b));
+  LB_TRY(stream_wait(ctx, sl, 0, 1, 1));
+  LB_TRY(enqueue_lines(ctx, sl, plan, b));
+  LB_TRY(enqueue_decode(ctx, sl, plan, b));
+  LB_TRY(enqueue_req_status(ctx, sl, plan, b));
+  LB_TRY(enqueue_sums(ctx, sl, plan, b));
+  LB_TRY(stream_wait(ctx, sl, 1, 0, 2));
+  LB_TRY(enqueue_accumulate(ctx, sl, plan, b));
+  fill_state(sl.ps, plan, b);
+  if (plan.merged) {
+    bool tails = true;
+    LB_TRY(enqueue_merged(ctx, sl, plan, b, &tails));
+    if (!tails) return LB_OK;
   }
   return run_tails(ctx, sl);
 }
 
-// lanes per set of a lone call's step-major accumulation: 4 up to 16,384 sets, 2 up to 32,768 (the
-// call's lanes then fill at most one wave per SIMD), 1 above (profiles/r06/level_probe_r06x.json:
-// 4,096 ... 16,384 sets 16.7-17.4 ms unsplit, 14.1-15.0 split in 4)
-static uint32_t step_split_for(uint32_t n_sets) { return n_sets <= 16384u ? 4u : n_sets <= 32768u ? 2u : 1u; }
-
-// k_level_part's workgroups per level: one request per thread (a merged call's requests are
-// mostly small), and about two lanes per thread when one large request holds the call
-static uint32_t level_blocks(uint32_t n_sets, uint32_t n_req, bool wide) {
-  // (wide, a lone call: about one lane per thread -- the products all in the wave-cooperative
-  // passes, the fastest for the call; otherwise about two, one lane product each: less work)
-  const uint32_t w = wide ? (4 * n_req > n_sets / 32u ? 4 * n_req : n_sets / 32u)
-                          : (n_req > n_sets / 126u ? n_req : n_sets / 126u);
-  const uint32_t b = (w + 255u) / 256u;
-  return b < 1u ? 1u : b > 8u ? 8u : b;
-}
-
+// The workspace a call of at most n_req requests and n_sets sets can take, whichever path and
+// switches it runs with (a slab is sized before its call's lone / partial state is known, and
+// for later calls: the same-message phase 2, the priority slot).  + 255: the first buffer's
+// alignment when the slab's fill at the call is not a multiple of 256.
 size_t pipeline_ws_bytes(const lb_ctx* ctx, uint32_t n_req, uint32_t n_sets) {
-  size_t ns = n_sets ? n_sets : 1;
-  // (+ the bucket MSM: 2 W keys + 2 W sorted entries and 2 W / T chunk partials per set)
-  // (+ the steps organisation: size histogram / cursors / gt / row offsets and the lanes' G values)
-  size_t per_set = sizeof(g2j) * 5 + sizeof(g1j) * 2 + sizeof(fp12) + 3 + 16 * 256 / 64 + 16 + 576 +
-                   (size_t)LB_MILLER_LINES * 72 * 4 + 4 * LB_MSM_W * 4 +
-                   (2 * LB_MSM_W * sizeof(g2j)) / (ns <= ctx->msm_short_max ? ctx->msm_t_lone : LB_MSM_T) + 1;
-  // (+ the halves of a split Miller accumulation: 2 fp12, 2 flags, 2 offsets)
-  size_t per_req = sizeof(g2a) + 8 * sizeof(fp12) + 1 + 4 + 8 + 8 + 4 * 256 / 64 + (size_t)LB_MILLER_LINES * 72 * 4 +
-                   (size_t)LB_RTAIL_NIN * 64 + 4 + 2 * 256 / 64;  // (+ k_lp_rtail's records and flag)
-  // (+ a lone call's bit-sum program records: 8 + 1 + 1/8 points of 6 records per level-0 instance)
-  const size_t msm_fixed = (size_t)(2 * LB_MSM_BUCKETS + LB_MSM_POS) * sizeof(g2j) + 4 * (LB_MSM_BUCKETS + 1) * 4 +
-                           8 * 256 + (size_t)LB_MSM_BITS_INST * (LB_MSM_BITS_GROUP + 1 + 1) * 6 * 64 + 3 * 256;
-  // (+ the merged check's round-program records, k_lp_mtail)
-  // (+ the level products' partials: 63 x 256 B of k_level_part, an eighth of that for the
-  // first k_level_wc pass, their flags)
-  // (+ the G values of a split accumulation, up to 4 lanes per set: LB_STEP_SPLIT may force 4 at
-  // any size -- 3 more G per set, and 4x the lanes for the level partials)
-  const size_t lvl_per = (size_t)level_blocks(n_sets * 4u, n_req, true) * 256;
-  const size_t lvl = 63 * (lvl_per + (lvl_per + LB_LVL_GROUP - 1) / LB_LVL_GROUP) * sizeof(fp12) + 2 * 63 * lvl_per +
-                     4 * 256;
-  return ns * per_set + (size_t)(n_req + 1) * per_req + msm_fixed + 64 * sizeof(fp12) + 80 * 256 + 4096 +
-         (size_t)(LB_MTAIL_NIN + 12) * 64 + 512 + lvl + ns * 3 * 576 +
-         (ns <= std::max(ctx->lp_dec_max, ctx->lp_hf_max) ? ns * (6 * 64 + 5 * 4 + 1 + 18 * 64) + 7 * 256 : 0) +  // (+ a lone call's
-                                                                                      // decode / hash records)
-         (ns <= ctx->lp_lines_max ? ns * (9 + LB_LP_LINES_NOUT) * 64 + 2 * 256 : 0);  // (+ its line records)
+  return layout_pipeline(plan_upper(ctx->cfg, n_req, n_sets)).bytes + 255;
 }
 
 int validate_batch(lb_ctx* ctx, const lb_request_batch* b) {
@@ -1216,9 +1148,8 @@ int slot_copy(lb_ctx* ctx, Slot& sl, void* dst, const void* src, size_t n, hipMe
   if (!n) return LB_OK;
   if (ctx->prio_kcopy && &sl == &ctx->prio() && n < (1u << 30)) {
     const size_t blocks = (n / 16 + 255) / 256;
-    hipLaunchKernelGGL(k_copy_bytes, dim3(blocks < 1 ? 1 : blocks > 512 ? 512 : (unsigned)blocks), dim3(256), 0, st,
-                       (const uint8_t*)src, (uint8_t*)dst, (uint32_t)n);
-    LB_HIP(hipGetLastError());
+    LB_ENQUEUE(st, k_copy_bytes, blocks < 1 ? 1 : blocks > 512 ? 512 : (unsigned)blocks, 256, (const uint8_t*)src,
+               (uint8_t*)dst, (uint32_t)n);
     return LB_OK;
   }
   LB_HIP(hipMemcpyAsync(dst, src, n, kind, st));
@@ -1520,61 +1451,15 @@ static int create_ctx(int device, lb_ctx** out_ctx, bool lane) {
     if (v >= 1 && v <= lb_ctx::kMaxSlots) ctx->n_slots = v;
   }
   if (lane) ctx->n_slots = 1;  // a latency-lane context: its priority lane (+ one slot for helpers)
-  if (const char* e = getenv("LB_MILLER"))
-    ctx->miller_mode = strcmp(e, "lane") == 0 ? 1 : strcmp(e, "lines") == 0 ? 2 : strcmp(e, "wave") == 0 ? 3 : 0;
-  if (const char* e = getenv("LB_TAIL")) ctx->tail_wave = strcmp(e, "lane") != 0;
-  if (const char* e = getenv("LB_MERGE_MIN")) ctx->merge_min_req = (uint32_t)atoi(e);
-  if (const char* e = getenv("LB_MSM_MIN")) ctx->msm_min_sets = (uint32_t)atoi(e);
-  if (const char* e = getenv("LB_LINES_MIN")) ctx->lines_min_sets = (uint32_t)atoi(e);
-  if (const char* e = getenv("LB_LEVEL")) ctx->level_wc = atoi(e) != 0;
-  if (const char* e = getenv("LB_MSM_LANES")) ctx->msm_lanes = atoi(e) != 0;
-  if (const char* e = getenv("LB_WIDE_TAIL")) ctx->wide_tail = atoi(e) != 0;
-  if (const char* e = getenv("LB_MSM_BITS_LP")) ctx->msm_bits_lp = atoi(e) != 0;
+  config_from_env(ctx->cfg, [](const char* name) -> const char* { return getenv(name); });
   if (const char* e = getenv("LB_SM_LP_DECODE")) ctx->sm_lp_decode = atoi(e) != 0;
   if (const char* e = getenv("LB_SM_RANDOMIZED")) ctx->sm_mode = atoi(e) == 1 ? LB_SM_RANDOMIZED : LB_SM_PLAIN;
-  if (const char* e = getenv("LB_LP_DECODE")) ctx->lp_decode = atoi(e) != 0;
-  if (const char* e = getenv("LB_LP_HASH_FINISH")) ctx->lp_hash_finish = atoi(e) != 0;
-  if (const char* e = getenv("LB_LP_LINES")) ctx->lp_lines = atoi(e) != 0;
-  if (const char* e = getenv("LB_MSM_SHORT")) ctx->msm_short = atoi(e) != 0;
-  if (const char* e = getenv("LB_LP_HASH_FULL")) ctx->lp_hash_full = (uint32_t)strtoul(e, nullptr, 10);
-  if (const char* e = getenv("LB_LP_NARROW")) ctx->lp_narrow = (uint32_t)strtoul(e, nullptr, 10);
-  if (const char* e = getenv("LB_LP_DEC_MAX")) ctx->lp_dec_max = (uint32_t)strtoul(e, nullptr, 10);
-  if (const char* e = getenv("LB_LP_HF_MAX")) ctx->lp_hf_max = (uint32_t)strtoul(e, nullptr, 10);
-  if (const char* e = getenv("LB_LP_LINES_MAX")) ctx->lp_lines_max = (uint32_t)strtoul(e, nullptr, 10);
-  if (const char* e = getenv("LB_MSM_SHORT_MAX")) ctx->msm_short_max = (uint32_t)strtoul(e, nullptr, 10);
-  if (const char* e = getenv("LB_MSM_T_LONE")) {
-    const unsigned long t = strtoul(e, nullptr, 10);
-    if (t >= 1 && t <= LB_MSM_T) ctx->msm_t_lone = (uint32_t)t;
-  }
-  if (const char* e = getenv("LB_STEP_SPLIT")) {
-    const int v = atoi(e);
-    ctx->step_split = (v == 1 || v == 2 || v == 4) ? (uint32_t)v : 0u;
-  }
-  if (const char* e = getenv("LB_WAVE_MAX")) ctx->wave_max_sets = (uint32_t)atoi(e);
-  if (const char* e = getenv("LB_MTAIL")) ctx->mtail_lp = atoi(e) != 0;
-  if (const char* e = getenv("LB_RTAIL")) ctx->rtail_lp = atoi(e) != 0;
-  if (const char* e = getenv("LB_TP_RELEASE")) ctx->tp_release = ctx->tp_release_cfg = atoi(e) != 0;
   if (const char* e = getenv("LB_TP_PAUSE")) ctx->tp_pause_calls = (uint32_t)atoi(e);
   if (const char* e = getenv("LB_FAULT_RERUN")) ctx->fault_rerun = atoi(e) != 0;
   if (const char* e = getenv("LB_GT_LP")) ctx->gt_lp = atoi(e) != 0;
   if (const char* e = getenv("LB_PRIO_KCOPY")) ctx->prio_kcopy = atoi(e) != 0;
-  if (const char* e = getenv("LB_LP_MAX")) {
-    const long v = atol(e);  // clamped like lb_set_latency_path: the product tree's 2^LB_LP_TREE_LEVELS sets
-    ctx->lp_max_sets = v <= 0 ? 0u : v < (1l << LB_LP_TREE_LEVELS) ? (uint32_t)v : (1u << LB_LP_TREE_LEVELS);
-    ctx->lp_explicit = true;
-  }
-  if (const char* e = getenv("LB_LP_LONE_MAX")) ctx->lp_lone_max = (uint32_t)strtoul(e, nullptr, 10);
-  if (const char* e = getenv("LB_LINES_WAVES")) ctx->lines_waves = ctx->lines_waves_small = atoi(e) == 1 ? 1 : 2;
-  if (const char* e = getenv("LB_ACC_SPLIT")) ctx->acc_split = atoi(e) ? 1 : 0;
-  if (const char* e = getenv("LB_ACC")) ctx->acc_steps = strcmp(e, "pairs") ? 1 : 0;
   if (const char* e = getenv("LB_DAG")) ctx->dag = atoi(e) != 0;
-  if (const char* e = getenv("LB_STEP_MODE")) ctx->step_mode = atoi(e);
-  if (const char* e = getenv("LB_STEP_WAVES")) ctx->step_waves = atoi(e) == 2 ? 2 : 1;
   if (const char* e = getenv("LB_STAGE_EVENTS")) ctx->stage_events = atoi(e) != 0;
-  if (const char* e = getenv("LB_ACC_LPR")) {
-    const int v = atoi(e);
-    if (v == 64 || v == 32 || v == 16) ctx->acc_lpr = v;
-  }
   for (int s = 0; s < lb_ctx::kMaxSlots; s++)
     ctx->streams_per_slot[s] = lane ? 1 : ctx->n_slots <= 2 ? 2 : (ctx->n_slots == 3 && s == 0) ? 2 : 1;
   ctx->streams_per_slot[ctx->n_slots] = 1;  // the priority lane
@@ -1732,15 +1617,16 @@ static int create_ctx(int device, lb_ctx** out_ctx, bool lane) {
   // the latency path's round programs (2.6 MB) are uploaded here, before any call is in
   // flight: a synchronous copy on the first latency-path call would wait for the
   // throughput calls already running on blocking (CU-masked) streams
-  if (ok && (ctx->lp_max_sets || ctx->mtail_lp || ctx->gt_lp || ctx->rtail_lp) && lp_ensure(ctx) != LB_OK) ok = false;
+  if (ok && (ctx->cfg.lp_max_sets || ctx->cfg.mtail_lp || ctx->gt_lp || ctx->cfg.rtail_lp) && lp_ensure(ctx) != LB_OK)
+    ok = false;
   // the priority slot's staging and workspace sized here for a latency-path call of
   // lp_max_sets sets (16 keys each by bytes): growing them later frees the old buffers,
   // and hipFree / hipHostFree synchronize the device -- the call would wait for every
   // throughput call in flight (the node leg's first 128-set priority job under load took
   // 0.9-1.5 s, profiles/r05/node_q/)
-  if (ok && ctx->lp_max_sets) {
+  if (ok && ctx->cfg.lp_max_sets) {
     Slot& pl = ctx->slots[ctx->n_slots];
-    const size_t ns = ctx->lp_max_sets, in = ns * (32 + 192 + 16 + 16 * 96) + 65536, out = 3 * ns + 4096;
+    const size_t ns = ctx->cfg.lp_max_sets, in = ns * (32 + 192 + 16 + 16 * 96) + 65536, out = 3 * ns + 4096;
     ok = ensure_pin(ctx, pl, in + out) == LB_OK && ensure_ws(ctx, pl, in + out + pipeline_ws_bytes(ctx, ns, ns)) == LB_OK;
   }
   if (!ok) {
@@ -1905,7 +1791,7 @@ static void pick_streams(lb_ctx* ctx, Slot& sl) {
 // a two-phase call's record (LB_TP_RELEASE; the legacy mode keeps only the ticket ring)
 static void tp_record(lb_ctx* ctx, uint64_t ticket, const lb_request_batch* b, bool device, uint8_t* valid,
                       uint8_t* err, uint8_t* sst) {
-  if (!ctx->tp_release) return;
+  if (!ctx->cfg.tp_release) return;
   // (the ticket ring too: a finish of a ticket whose record was reused -- finished or waited
   // for by then, tp_reusable -- is a no-op, not an error)
   ctx->two_phase[ctx->two_phase_pos] = ticket;
@@ -1947,18 +1833,17 @@ static int submit_device(lb_ctx* ctx, Slot& sl, const lb_request_batch* b, uint8
   if (!partial) borrow_idle_stream(ctx, sl);  // (a pending two-phase call never holds a lent slot)
   LB_TRY(ensure_ws(ctx, sl, pipeline_ws_bytes(ctx, b->n_requests, b->n_sets)));
   Bump ws{sl.d_ws, 0, sl.ws_cap};
-  uint8_t* d_partial = partial ? ws.take<uint8_t>(LB_GT_BYTES) : nullptr;
   LB_TRY(begin_call(ctx, sl));
   if (b->n_requests)
     LB_TRY(run_pipeline(ctx, sl, b->n_requests, b->n_sets, b->request_offsets, b->pubkeys, b->pk_offsets,
                         b->pubkey_indices, b->messages, b->signatures, b->sig_offsets, b->seed, d_valid, d_req_err,
-                        d_set_status, ws, d_partial));
+                        d_set_status, ws, partial));
   else if (partial) {  // nothing to verify: the partial is the identity (1 in Fp12)
     memset(sl.h_partial, 0, LB_GT_BYTES);
     sl.h_partial[47] = 1;
     LB_HIP(hipEventRecord(sl.partial_ev, sl.st[0]));
     sl.ps = PipeState{};
-    sl.partial_pending = !ctx->tp_release;
+    sl.partial_pending = !ctx->cfg.tp_release;
   }
   LB_TRY(end_call_async(ctx, sl));
   *out_ticket = sl.ticket;
@@ -2068,7 +1953,6 @@ static int submit_host(lb_ctx* ctx, Slot& sl, const lb_request_batch* b, uint8_t
   uint8_t* d_valid = ws.take<uint8_t>(nr ? nr : 1);
   uint8_t* d_err = ws.take<uint8_t>(nr ? nr : 1);
   uint8_t* d_sst = ws.take<uint8_t>(ns ? ns : 1);
-  uint8_t* d_partial = partial ? ws.take<uint8_t>(LB_GT_BYTES) : nullptr;
   LB_TRY(begin_call(ctx, sl));
   sl.dv_valid = d_valid;
   sl.dv_err = d_err;
@@ -2097,14 +1981,14 @@ static int submit_host(lb_ctx* ctx, Slot& sl, const lb_request_batch* b, uint8_t
   if (nr) {
     LB_TRY(run_pipeline(ctx, sl, nr, ns, d_req, by_index ? d_rows : d_pks, d_pko,
                         by_index ? (const uint32_t*)d_pks : nullptr, d_msg, d_sig, d_sigo, d_seed, d_valid, d_err, d_sst,
-                        ws, d_partial));
+                        ws, partial));
     t_pipe = ms_since(t0);
   } else if (partial) {
     memset(sl.h_partial, 0, LB_GT_BYTES);
     sl.h_partial[47] = 1;
     LB_HIP(hipEventRecord(sl.partial_ev, sl.st[0]));
     sl.ps = PipeState{};
-    sl.partial_pending = !ctx->tp_release;
+    sl.partial_pending = !ctx->cfg.tp_release;
   }
   LB_TRY(end_call_async(ctx, sl));
   *out_ticket = sl.ticket;
@@ -2172,9 +2056,9 @@ int lb_verify_requests_partial_async(lb_ctx* ctx, const lb_request_batch* b, uin
   if (!out_valid || !out_req_err) return LB_ERR_INVALID_ARGUMENT;
   LB_HIP(hipSetDevice(ctx->device));
   LB_TRY(sm_pump(ctx));
-  ctx->tp_release = ctx->tp_release_cfg && ctx->tp_pause == 0;
+  ctx->cfg.tp_release = ctx->cfg.tp_release_cfg && ctx->tp_pause == 0;
   if (ctx->tp_pause) ctx->tp_pause--;
-  if (ctx->tp_release && !tp_reusable(ctx, ctx->tp[ctx->next_ticket % lb_ctx::kTwoPhaseRing])) {
+  if (ctx->cfg.tp_release && !tp_reusable(ctx, ctx->tp[ctx->next_ticket % lb_ctx::kTwoPhaseRing])) {
     // (the ticket this call would take is end_call_async's next_ticket: no ticket is issued
     // in between)
     ctx->err = "two-phase ring full: the call " +
@@ -2292,7 +2176,7 @@ int lb_verify_requests_finish(lb_ctx* ctx, uint64_t ticket, int merged_ok) {
     ctx->err = "ticket is not a two-phase call";
     return LB_ERR_INVALID_ARGUMENT;
   }
-  if (!merged_ok && ctx->tp_release_cfg) ctx->tp_pause = ctx->tp_pause_calls;  // (failures go on: stay legacy)
+  if (!merged_ok && ctx->cfg.tp_release_cfg) ctx->tp_pause = ctx->tp_pause_calls;  // (failures go on: stay legacy)
   return finish_partial(ctx, *sl, merged_ok != 0);
 }
 
@@ -2326,15 +2210,11 @@ int lb_gt_check(lb_ctx* ctx, uint32_t n, const uint8_t* partials576, int32_t* ou
     // the product (one wave), then the final exponentiation as a round program on one
     // workgroup (~420 rounds) instead of the one-wave chain
     uint32_t* d_rec = reinterpret_cast<uint32_t*>(ctx->d_aux + 256 + (((size_t)n * LB_GT_BYTES + 255) & ~(size_t)255));
-    hipLaunchKernelGGL(k_gt_prod, dim3(1), dim3(TPB), 0, ctx->aux_stream, n, (const uint8_t*)d_in, d_rec, d_out);
-    LB_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_lp_final_lane, dim3(1), dim3(LB_LP_TPB), 0, ctx->aux_stream,
-                       (const uint32_t*)(ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_FINAL_LANE].off), (const uint32_t*)d_rec,
-                       d_out);
-    LB_HIP(hipGetLastError());
+    LB_ENQUEUE(ctx->aux_stream, k_gt_prod, 1, TPB, n, (const uint8_t*)d_in, d_rec, d_out);
+    LB_ENQUEUE(ctx->aux_stream, k_lp_final_lane, 1, LB_LP_TPB,
+               (const uint32_t*)(ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_FINAL_LANE].off), (const uint32_t*)d_rec, d_out);
   } else {
-    hipLaunchKernelGGL(k_gt_check, dim3(1), dim3(TPB), 0, ctx->aux_stream, n, (const uint8_t*)d_in, d_out);
-    LB_HIP(hipGetLastError());
+    LB_ENQUEUE(ctx->aux_stream, k_gt_check, 1, TPB, n, (const uint8_t*)d_in, d_out);
   }
   LB_HIP(hipMemcpyAsync(ctx->h_aux, d_out, 2, hipMemcpyDeviceToHost, ctx->aux_stream));
   LB_HIP(hipStreamSynchronize(ctx->aux_stream));
@@ -2423,7 +2303,7 @@ int lb_verify_requests_device(lb_ctx* ctx, const lb_request_batch* b, uint8_t* d
   if (!d_valid || !d_req_err) return LB_ERR_INVALID_ARGUMENT;
   LB_HIP(hipSetDevice(ctx->device));
   uint64_t t = 0;
-  if (b->n_sets <= ctx->lp_max_sets && !(lp_lone_rule(ctx, b->n_sets) && !any_slot_busy(ctx))) {
+  if (b->n_sets <= ctx->cfg.lp_max_sets && !(lp_lone_rule(ctx->cfg, b->n_sets) && !any_slot_busy(ctx))) {
     // latency path: the priority lane, beside any calls in flight
     LB_TRY(submit_device(ctx, ctx->prio(), b, d_valid, d_req_err, d_set_status, false, &t));
     return lb_wait(ctx, t, stats);
@@ -2445,7 +2325,7 @@ int lb_verify_requests(lb_ctx* ctx, const lb_request_batch* b, uint8_t* out_vali
     return LB_OK;
   }
   uint64_t t = 0;
-  if (b->n_sets <= ctx->lp_max_sets && !(lp_lone_rule(ctx, b->n_sets) && !any_slot_busy(ctx))) {
+  if (b->n_sets <= ctx->cfg.lp_max_sets && !(lp_lone_rule(ctx->cfg, b->n_sets) && !any_slot_busy(ctx))) {
     // latency path: the priority lane, beside any calls in flight
     LB_TRY(submit_host(ctx, ctx->prio(), b, out_valid, out_req_err, out_set_status, false, &t));
     return lb_wait(ctx, t, stats);
@@ -3186,13 +3066,11 @@ int sm_advance_launch(lb_ctx* ctx, Slot& sl, bool block) {
         return LB_ERR_OUT_OF_MEMORY;
       }
       LB_HIP(hipMemcpyAsync(d_rset, m.h_rset, sizeof(uint32_t) * 2 * (size_t)ns, hipMemcpyHostToDevice, sl.st[0]));
-      hipLaunchKernelGGL(k_sm_retry_gather, dim3(blocks_for(nr)), dim3(TPB), 0, sl.st[0], nr, (const uint32_t*)d_rset,
-                         (const uint32_t*)(d_rset + ns), m.d_sig, m.d_sst, m.d_msgs,
-                         m.by_index ? (const uint32_t*)m.d_pks : (const uint32_t*)nullptr, d_rsig, d_rst, d_rmsg,
-                         d_ridx, d_rreq);
-      LB_HIP(hipGetLastError());
+      LB_ENQUEUE(sl.st[0], k_sm_retry_gather, blocks_for(nr), TPB, nr, (const uint32_t*)d_rset,
+                 (const uint32_t*)(d_rset + ns), m.d_sig, m.d_sst, m.d_msgs,
+                 m.by_index ? (const uint32_t*)m.d_pks : (const uint32_t*)nullptr, d_rsig, d_rst, d_rmsg, d_ridx, d_rreq);
       LB_TRY(run_pipeline(ctx, sl, nr, nr, d_rreq, m.by_index ? m.d_rows : m.d_pks, nullptr, d_ridx, d_rmsg, nullptr,
-                          nullptr, m.d_seed, d_rvalid, d_rerr, nullptr, ws, nullptr, d_rsig, d_rst));
+                          nullptr, m.d_seed, d_rvalid, d_rerr, nullptr, ws, false, d_rsig, d_rst));
       LB_HIP(hipMemcpyAsync(m.h_rout, d_rvalid, nr, hipMemcpyDeviceToHost, sl.st[0]));
       LB_HIP(hipMemcpyAsync(m.h_rout + al256(ns), d_rerr, nr, hipMemcpyDeviceToHost, sl.st[0]));
       if (m.agg) {  // behind phase 2: the retried sets that verified alone join the sums
@@ -3668,8 +3546,8 @@ int lb_set_latency_path(lb_ctx* ctx, uint32_t max_sets) {
   if (!ctx) return LB_ERR_INVALID_ARGUMENT;
   // (k_lp_verify's product tree has LB_LP_TREE_LEVELS levels of arrival counters: a
   // request longer than 2^levels sets would count past them)
-  ctx->lp_max_sets = max_sets < (1u << LB_LP_TREE_LEVELS) ? max_sets : (1u << LB_LP_TREE_LEVELS);
-  ctx->lp_explicit = true;
+  ctx->cfg.lp_max_sets = max_sets < (1u << LB_LP_TREE_LEVELS) ? max_sets : (1u << LB_LP_TREE_LEVELS);
+  ctx->cfg.lp_explicit = true;
   return LB_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/lodestar_bls.h"
+#include "bls_limits.h"
 #include "bls_pairing.h"
 
 
@@ -53,17 +54,7 @@ static constexpr int TPB = 64;  // one wave per workgroup: flexible residency at
 #endif
 
 
-// Bucket MSM of the merged check (k_msm.hip): signed digits of LB_MSM_C bits in
-// LB_MSM_W windows of the 32-bit GLV half-scalars, LB_MSM_NB buckets per window,
-// chunks of <= LB_MSM_T entries, bit positions 0 .. LB_MSM_POS - 1.
-#define LB_MSM_C 11
-#define LB_MSM_W 3
-#define LB_MSM_NB 1024u
-#define LB_MSM_BUCKETS (LB_MSM_W * LB_MSM_NB)
-#define LB_MSM_T 16u
-#define LB_MSM_T_LONE 4u  // (a lone call of at most LB_LP_DEC_MAX sets: shorter chunk chains, more chunks)
-#define LB_MSM_POS 33u
-#define LB_MSM_NONE 0xffffffffu
+// (the bucket MSM's limits LB_MSM_*: bls_limits.h)
 
 namespace lb {
 // One lane's tower value in an LDS tree, padded so the record stride is an odd number of
@@ -293,8 +284,6 @@ __global__ void __launch_bounds__(TPB, LB_W_SCALAR) k_msm_chunks(uint32_t max_ch
 __global__ void __launch_bounds__(TPB, LB_W_SCALAR) k_msm_buckets(const uint32_t* __restrict__ coff,
                                                                   const g2j* __restrict__ csum, g2j* __restrict__ bsum,
                                                                   uint32_t lanes);
-static constexpr uint32_t LB_MSM_BLANES = 4;      // k_msm_buckets: lanes per bucket
-static constexpr uint32_t LB_MSM_BITS_TPB = 256;  // k_msm_bits: threads per bit position
 template <int T>  // (T threads per bit position: TPB, or LB_MSM_BITS_TPB for a lone call)
 __global__ void __launch_bounds__(T, T == TPB ? LB_W_SCALAR : 1) k_msm_bits(const g2j* __restrict__ bsum,
                                                                            g2j* __restrict__ G);
@@ -327,8 +316,7 @@ __global__ void __launch_bounds__(256, 1) k_level_prod(uint32_t n_req, uint32_t 
                                                        const uint8_t* __restrict__ req_bad,
                                                        const uint32_t* __restrict__ lines, fp12* __restrict__ Pl);
 // the level products in two stages (round 6): lane products of each level's share, then
-// wave-cooperative products of groups of LB_LVL_GROUP partials (k_steps.hip)
-static constexpr uint32_t LB_LVL_GROUP = 8;
+// wave-cooperative products of groups of LB_LVL_GROUP partials (k_steps.hip; bls_limits.h)
 __global__ void __launch_bounds__(256, 1) k_level_part(uint32_t n_req, uint32_t n_sets, Rows R,
                                                        const uint32_t* __restrict__ req_off,
                                                        const uint32_t* __restrict__ G,

@@ -5,11 +5,8 @@
 #include <stdint.h>
 
 #include "bls_kernels.h"
+#include "bls_limits.h"
 
-#ifndef LB_LP_ROWS
-#define LB_LP_ROWS 32                     // units per round = 16-lane rows per workgroup
-#endif
-#define LB_LP_TPB (LB_LP_ROWS * 16)       // 8 waves: 2 per SIMD (256 VGPRs for the one-lane inversion)
 // k_lp_verify's waves per SIMD target: 4 = two workgroups per CU (128 VGPRs, 12 spilled;
 // LDS 2 x 68 KB): 512-set calls 6.9 -> 4.6 ms, 1024-set 12.4 -> 8.5 ms, 1 and 128 sets
 // unchanged (profiles/r05/lp_direct/lp_v*); 2 = one per CU (152 VGPRs)
@@ -28,7 +25,6 @@
 #define LB_LP_CHUNK 2048                  // stream words fetched per round (4 per thread; rounds average
                                           // ~0.9k words, the final program ~1.04k)
 #define LB_LP_HDR 10                      // header words of an encoded program
-#define LB_LP_TREE_LEVELS 20              // product-tree levels (requests up to 2^20 sets)
 
 #define LB_LP_OP_MUL 0
 #define LB_LP_OP_LIN 1
@@ -62,22 +58,9 @@
 #define LB_LP_PROG_HASH_FULL 17  // a lone mid-size call's whole hash_to_G2 curve part (k_lp_hash, 8 rows)
 #define LB_LP_NPROGS 18
 #define LB_LP_HASH_REGS 384  // gen_lp.py MAX_REGS_HASH
-#define LB_LP_NARROW_ROWS 8  // gen_lp.py DEC_ROWS
-#define LB_LP_LINES_MAX 5120  // lone steps calls of at most this many sets store their lines via k_lp_lines (6,144: -0.5 ms)
-#define LB_LP_LINES_NOUT (68 * 6)
-#define LB_LP_HF_ROWS 16           // gen_lp.py HF_ROWS
-#define LB_LP_HF_MAX 3072          // lone calls of at most this many sets finish their hash on k_lp_hf
-#define LB_LP_DEC_ROWS 8          // gen_lp.py DEC_ROWS
 #define LB_LP_DEC_REGS 128        // gen_lp.py MAX_REGS_DEC
 #define LB_SM_DEC_MAX 512         // packages of at most this many signatures decode on k_lp_dec
-#define LB_LP_DEC_MAX 5120        // ... and lone pipeline calls of at most this many sets
-#define LB_MSM_BITS_GROUP 8      // lpgen/bls.py MSM_BITS_GROUP
-#define LB_MSM_BITS_INST (LB_MSM_POS * (LB_MSM_NB / 2 / LB_MSM_BITS_GROUP))  // level-0 instances: 33 x 64
-#define LB_RTAIL_NIN 16                 // rtail inputs: F_k (12 Fp), S_k affine (4 Fp); inflag S_inf
 #define LB_LP_RTAIL_REGS 512            // (its program holds ~240 registers: 32 KB of LDS)
-#define LB_MTAIL_LEVELS 63                  // the step-major accumulation's Horner levels (k_steps.hip)
-#define LB_MTAIL_NIN (12 * LB_MTAIL_LEVELS + 6 * LB_MSM_POS)  // mtail inputs: the 63 level products, the MSM's
-                                                              // 33 bit sums
 
 namespace lb {
 // k_lp.hip: instance b (one workgroup of LB_LP_TPB threads) runs the round program at
@@ -112,7 +95,6 @@ struct LpCall {
   // written (zeroed; [2] and [3] by the workgroup that writes it)
   unsigned long long* clk;
 };
-static constexpr uint32_t LB_LP_NIN = 11, LB_LP_NFL = 67;  // set program inputs / input flags
 __global__ void __launch_bounds__(TPB) k_lp_prep(uint32_t n, const uint32_t* __restrict__ req_off, uint32_t n_req,
                                                  const uint8_t* __restrict__ msgs, const uint8_t* __restrict__ sigs,
                                                  const uint32_t* __restrict__ sig_off, const g1j* __restrict__ pk,
