@@ -53,8 +53,8 @@ LB_DEV void wc_init_tables(wc_smem& S) {
 }
 
 // ---- lazy accumulation: a lane sums up to 8 (|coef|-weighted) canonical terms
-// (the signed sum plus the negative weight times p stays in [0, 8p), 8p < 2^384),
-// then reduces once with conditional subtractions of 4p, 2p, p.
+// (the signed sum plus the negative weight times p stays in [0, w p], w <= 8, and below
+// 8p < 2^384), then reduces once with conditional subtractions of 4p, 2p, p.
 static constexpr uint32_t WC_P2[12] = LB_P2_LIMBS;
 static constexpr uint32_t WC_P4[12] = LB_P4_LIMBS;
 
@@ -109,9 +109,14 @@ LB_DEV void lz_sum(fp& r, const uint16_t* term, int t0, int t1, Val val, bool ca
     a.l[j] = (uint32_t)t;
     carry = t >> 32;  // arithmetic: a limb's partial result may be negative
   }
-  if (w > 4) lz_csub(a, WC_P4);
-  if (w > 2) lz_csub(a, WC_P2);
-  if (canonical && w > 1) lz_csub(a, P_);
+  // a lies in [0, w p], the upper end included: a form whose terms are all negative and all
+  // zero sums to kneg p = w p (the conjugate of a zero coefficient is the plain case).  So
+  // the subtraction of 4p, 2p, p starts AT w = 4, 2, 1: [0, 4p] - 4p and [0, 2p] - 2p leave
+  // [0, 4p) and [0, 2p), and w = 1 reduces p to 0.  (w = 8 all negative would need 8p;
+  // gen_wc12.py asserts no form or chunk is one.)
+  if (w >= 4) lz_csub(a, WC_P4);
+  if (w >= 2) lz_csub(a, WC_P2);
+  if (canonical) lz_csub(a, P_);
 #pragma unroll
   for (int j = 0; j < 12; j++) r.l[j] = a.l[j];
 }

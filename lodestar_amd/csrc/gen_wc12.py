@@ -284,6 +284,12 @@ def chunks(term_list):
     return out
 
 
+def all_negative_full(term_list):
+    """A run of full weight whose coefficients are all negative: on all-zero terms lz_sum would
+    form CHUNK * p, one p above what its subtractions of 4p, 2p, p reduce (bls_wc12.h)."""
+    return all(c < 0 for c, _ in term_list) and sum(-c for c, _ in term_list) == CHUNK
+
+
 def main():
     path = sys.argv[1] if len(sys.argv) > 1 else "bls_wc12_tables.h"
     terms = []  # flat (coef, code)
@@ -298,17 +304,18 @@ def main():
         for x, y in P.prods:
             xoff.append(len(terms))
             tx = enc_terms(x, {"A"})
-            assert sum(abs(c) for c, _ in tx) <= CHUNK
+            assert sum(abs(c) for c, _ in tx) <= CHUNK and not all_negative_full(tx)
             terms += tx
             yoff.append(len(terms))
             ty = enc_terms(y, {"A"} if P.square else {"B"})
-            assert sum(abs(c) for c, _ in ty) <= CHUNK
+            assert sum(abs(c) for c, _ in ty) <= CHUNK and not all_negative_full(ty)
             terms += ty
         yoff.append(len(terms))  # sentinel after the last product's y terms
         coff, cs = [], []
         for o in out.flat():
             cs.append(len(coff))
             for ch in chunks(enc_terms(o, {"A", "B", "P"})):
+                assert not all_negative_full(ch), (name, ch)
                 coff.append(len(terms))
                 terms += ch
         cs.append(len(coff))

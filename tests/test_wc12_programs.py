@@ -2,48 +2,14 @@
 Fp products + linear combinations per operation) evaluated on random inputs
 against the oracle's Fp12 arithmetic.  CPU only: this pins the tables the
 GPU's k_tail kernel executes."""
-import importlib.util
-import os
 import random
 
 import pytest
 
 from oracle import bls12_381 as O
+from tests.wc12_helper import G, flat, run, unflat
 
 P = O.P
-_spec = importlib.util.spec_from_file_location(
-    "gen_wc12", os.path.join(os.path.dirname(__file__), "..", "lodestar_amd", "csrc", "gen_wc12.py"))
-G = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(G)
-
-
-def flat(f12):
-    out = []
-    for f6 in f12:
-        for f2 in f6:
-            out += [f2[0], f2[1]]
-    return out
-
-
-def unflat(v):
-    f2 = [(v[2 * k], v[2 * k + 1]) for k in range(6)]
-    return ((f2[0], f2[1], f2[2]), (f2[3], f2[4], f2[5]))
-
-
-def run(prog_fn, A, B):
-    prog, out = prog_fn()
-    env = {}
-
-    def ev(form):
-        acc = 0
-        for (kind, i), c in form.d.items():
-            v = A[i] if kind == "A" else B[i] if kind == "B" else env[i]
-            acc += c * v
-        return acc % P
-
-    for k, (x, y) in enumerate(prog.prods):
-        env[k] = ev(x) * ev(y) % P
-    return [ev(o) for o in out.flat()]
 
 
 def rnd12(r):
@@ -95,3 +61,20 @@ def test_frobenius(rng, k):
 def test_conj(rng):
     a = rnd12(rng)
     assert run(G.op_conj, a, a) == flat(O.f12_conj(unflat(a)))
+
+
+def test_no_all_negative_run_of_full_weight():
+    """lz_sum (bls_wc12.h) reduces [0, w p] for w < 8 and [0, 8p) for w = 8: a form or an
+    output chunk of weight 8 whose coefficients are all negative would reach 8p on zero terms."""
+    seen = 0
+    for name, fn in G.OPS:
+        prog, out = fn()
+        for x, y in prog.prods:
+            for form in (x, y):
+                assert not G.all_negative_full(G.enc_terms(form, {"A", "B"})), name
+        for o in out.flat():
+            for ch in G.chunks(G.enc_terms(o, {"A", "B", "P"})):
+                assert sum(abs(c) for c, _ in ch) <= G.CHUNK and not G.all_negative_full(ch), name
+                seen += all(c < 0 for c, _ in ch)
+    assert seen  # all-negative runs exist (the conjugate's outputs): the closed upper end matters
+    assert G.all_negative_full([(-3, 0), (-5, 1)]) and not G.all_negative_full([(-3, 0), (5, 1)])
