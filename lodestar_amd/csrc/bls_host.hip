@@ -112,33 +112,18 @@ struct SmState {
   bool active = false;
   int phase = 0;                     // 1: phase 1 in flight, 2: phase 2 (retries) in flight
   uint32_t nr = 0, retried_jobs = 0, fast_sets = 0;
-  bool by_index = false;
   uint32_t mode = LB_SM_PLAIN;       // the context's aggregation mode when the package was submitted
   uint32_t nj = 0, ns = 0;
   uint8_t* out_valid = nullptr;     // caller: n_sets verdicts
   uint8_t* out_job_fast = nullptr;  // caller (optional): n_jobs flags
-  const uint32_t* h_joff = nullptr;  // pinned copy of job_offsets
-  const uint8_t* h_res = nullptr;    // pinned phase-1 results: valid, err, job_bad, pk status (al(nj) each)
-  uint32_t* h_rset = nullptr;        // pinned: phase-2 set indices, then job indices (ns each)
-  uint8_t* h_rout = nullptr;         // pinned: phase-2 verdicts, errors (al(ns) each)
-  // device-resident phase-1 data
-  const uint8_t* d_pks = nullptr;    // 96-byte keys or u32 indices (by_index)
-  const uint8_t* d_rows = nullptr;   // by_index: the mixed package's key rows (or nullptr)
-  const g2j* d_sig = nullptr;        // decoded signatures (validate=true done once)
-  const uint8_t* d_sst = nullptr;
-  const uint8_t* d_msgs = nullptr;
-  const uint8_t* d_seed = nullptr;
-  size_t ws_off = 0;                 // bump offset after phase 1 (phase 2 allocates from here)
+  // the package's buffers of both phases -- device-resident inputs and decoded signatures, the
+  // pinned result rows and retry lists -- as offsets of the slot's slab and staging (bls_carve.h)
+  SmShape shape;
+  SmLayout lay;
   // lb_verify_same_message_batch_agg: the jobs' aggregate signatures (sm_job_sig, k_aggsig.hip)
-  bool agg = false;
+  bool agg = false, masked = false;  // (masked: the caller passed a mask)
   uint8_t* out_job_sig96 = nullptr;  // caller: n_jobs x 96
   uint32_t* out_job_count = nullptr; // caller: n_jobs
-  const uint8_t* h_agg = nullptr;    // pinned: 96 nj signature bytes, then (al) nj counts
-  const uint32_t* d_joff = nullptr;
-  const uint8_t* d_mask = nullptr;   // the caller's mask (or nullptr)
-  uint8_t* d_inc = nullptr;          // per-set include flags
-  uint8_t* d_agg96 = nullptr;
-  uint32_t* d_aggcnt = nullptr;
   int err = 0;                       // a failed phase-2 launch: reported by this ticket's wait
   std::string err_msg;
 };
@@ -173,7 +158,7 @@ struct Slot {
   // host-buffer calls: device outputs, their pinned copies and the caller's
   // buffers they are copied into when the call retires (finish_slot)
   uint8_t *dv_valid = nullptr, *dv_err = nullptr, *dv_sst = nullptr;
-  char* h_out = nullptr;
+  uint8_t *hv_valid = nullptr, *hv_err = nullptr, *hv_sst = nullptr;
   uint8_t *out_valid = nullptr, *out_err = nullptr, *out_sst = nullptr;
   uint32_t out_nr = 0, out_ns = 0;
   SmState sm;
@@ -354,18 +339,15 @@ namespace {
 
 inline uint32_t blocks_for(uint32_t n, uint32_t tpb = TPB) { return (n + tpb - 1) / tpb; }
 
-struct Bump {
+// A slot's slab as a pipeline call finds it: `fill` bytes are taken by the caller's own buffers
+// (bls_carve.h), run_pipeline lays its workspace out from there and moves the fill past it
+struct Slab {
   char* base;
-  size_t off = 0;
+  size_t fill;
   size_t cap;
-  template <class T>
-  T* take(size_t count) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = reinterpret_cast<T*>(base + off);
-    off += sizeof(T) * count;
-    return p;
-  }
 };
+template <class T>
+T* slab_at(char* base, size_t off) { return off == kCarveAbsent ? nullptr : reinterpret_cast<T*>(base + off); }
 
 int ensure_ws(lb_ctx* ctx, Slot& sl, size_t bytes) {
   if (bytes <= sl.ws_cap) return LB_OK;
@@ -451,22 +433,24 @@ int slot_copy(lb_ctx* ctx, Slot& sl, void* dst, const void* src, size_t n, hipMe
 int run_lp(lb_ctx* ctx, Slot& sl, uint32_t n_req, uint32_t n_sets, const uint32_t* d_req_off, const uint8_t* d_pks,
            const uint32_t* d_pk_off, const uint32_t* d_pk_idx, const uint8_t* d_msgs, const uint8_t* d_sigs,
            const uint32_t* d_sig_off, const uint8_t* d_seed, uint8_t* d_valid, uint8_t* d_req_err,
-           uint8_t* d_set_status, Bump& ws) {
+           uint8_t* d_set_status, Slab& ws) {
   LB_TRY(lp_ensure(ctx));
   const uint32_t ns = n_sets ? n_sets : 1;
-  g1j* d_pk = ws.take<g1j>(ns);
-  uint8_t* d_pk_st = ws.take<uint8_t>(ns);
-  uint32_t* d_in16 = ws.take<uint32_t>((size_t)ns * LB_LP_NIN * 16);
-  uint32_t* d_fl = ws.take<uint32_t>((size_t)ns * LB_LP_NFL);
-  uint8_t* d_sig_st = d_set_status ? d_set_status : ws.take<uint8_t>(ns);
-  uint32_t* d_setreq = ws.take<uint32_t>(ns);
-  uint32_t* d_F = ws.take<uint32_t>((size_t)ns * 12 * 16);
-  uint32_t* d_cnt = ws.take<uint32_t>((size_t)LB_LP_TREE_LEVELS * ns);
-  unsigned long long* d_clk = ws.take<unsigned long long>(4);
-  if (ws.off > ws.cap) {
+  const LpLayout lay = layout_lp(ns, !d_set_status, ws.fill);
+  if (lay.end > ws.cap) {
     ctx->err = "workspace overflow";
     return LB_ERR_OUT_OF_MEMORY;
   }
+  ws.fill = lay.end;
+  g1j* d_pk = slab_at<g1j>(ws.base, lay.off[LPB_PK]);
+  uint8_t* d_pk_st = slab_at<uint8_t>(ws.base, lay.off[LPB_PK_ST]);
+  uint32_t* d_in16 = slab_at<uint32_t>(ws.base, lay.off[LPB_IN16]);
+  uint32_t* d_fl = slab_at<uint32_t>(ws.base, lay.off[LPB_FL]);
+  uint8_t* d_sig_st = d_set_status ? d_set_status : slab_at<uint8_t>(ws.base, lay.off[LPB_SIG_ST]);
+  uint32_t* d_setreq = slab_at<uint32_t>(ws.base, lay.off[LPB_SETREQ]);
+  uint32_t* d_F = slab_at<uint32_t>(ws.base, lay.off[LPB_F]);
+  uint32_t* d_cnt = slab_at<uint32_t>(ws.base, lay.off[LPB_CNT]);
+  unsigned long long* d_clk = slab_at<unsigned long long>(ws.base, lay.off[LPB_CLK]);
   if (!n_sets) {  // every request empty: false (otherwise k_lp_prep zeroes the outputs)
     LB_HIP(hipMemsetAsync(d_valid, 0, n_req, sl.st[0]));
     LB_HIP(hipMemsetAsync(d_req_err, 0, n_req, sl.st[0]));
@@ -1064,7 +1048,7 @@ static void fill_state(PipeState& ps, const PipePlan& p, const PipeBufs& b) {
 int run_pipeline(lb_ctx* ctx, Slot& sl, uint32_t n_req, uint32_t n_sets, const uint32_t* d_req_off,
                  const uint8_t* d_pks, const uint32_t* d_pk_off, const uint32_t* d_pk_idx, const uint8_t* d_msgs, const uint8_t* d_sigs,
                  const uint32_t* d_sig_off, const uint8_t* d_seed, uint8_t* d_valid, uint8_t* d_req_err,
-                 uint8_t* d_set_status, Bump& ws, bool partial = false, const g2j* d_sig_pre = nullptr,
+                 uint8_t* d_set_status, Slab& ws, bool partial = false, const g2j* d_sig_pre = nullptr,
                  const uint8_t* d_sst_pre = nullptr) {
   PipeShape shape;
   shape.n_req = n_req;
@@ -1078,8 +1062,8 @@ int run_pipeline(lb_ctx* ctx, Slot& sl, uint32_t n_req, uint32_t n_sets, const u
   if (plan.latency_path)
     return run_lp(ctx, sl, n_req, n_sets, d_req_off, d_pks, d_pk_off, d_pk_idx, d_msgs, d_sigs, d_sig_off, d_seed,
                   d_valid, d_req_err, d_set_status, ws);
-  const PipeLayout lay = layout_pipeline(plan, ws.off);
-  if (ws.off + lay.bytes > ws.cap) {  // (the one capacity check: nothing is enqueued yet)
+  const PipeLayout lay = layout_pipeline(plan, ws.fill);
+  if (ws.fill + lay.bytes > ws.cap) {  // (the one capacity check: nothing is enqueued yet)
     ctx->err = "workspace overflow";
     return LB_ERR_OUT_OF_MEMORY;
   }
@@ -1096,7 +1080,7 @@ int run_pipeline(lb_ctx* ctx, Slot& sl, uint32_t n_req, uint32_t n_sets, const u
   b.valid = d_valid;
   b.req_err = d_req_err;
   bind_workspace(b, ws.base, lay, plan.lsplit);
-  ws.off += lay.bytes;
+  ws.fill += lay.bytes;
   if (d_sig_pre) b.sig = const_cast<g2j*>(d_sig_pre);
   if (d_sst_pre)
     b.sig_st = const_cast<uint8_t*>(d_sst_pre);
@@ -1160,10 +1144,9 @@ int slot_copy(lb_ctx* ctx, Slot& sl, void* dst, const void* src, size_t n, hipMe
 // (enqueued after the tails; the caller's buffers are filled in finish_slot).
 int enqueue_host_out(lb_ctx* ctx, Slot& sl) {
   if (!sl.out_valid) return LB_OK;
-  const size_t a = (sl.out_nr + 255) & ~(size_t)255;
-  LB_TRY(slot_copy(ctx, sl, sl.h_out, sl.dv_valid, sl.out_nr, hipMemcpyDeviceToHost, sl.st[0]));
-  LB_TRY(slot_copy(ctx, sl, sl.h_out + a, sl.dv_err, sl.out_nr, hipMemcpyDeviceToHost, sl.st[0]));
-  if (sl.out_ns) LB_TRY(slot_copy(ctx, sl, sl.h_out + 2 * a, sl.dv_sst, sl.out_ns, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_TRY(slot_copy(ctx, sl, sl.hv_valid, sl.dv_valid, sl.out_nr, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_TRY(slot_copy(ctx, sl, sl.hv_err, sl.dv_err, sl.out_nr, hipMemcpyDeviceToHost, sl.st[0]));
+  if (sl.out_ns) LB_TRY(slot_copy(ctx, sl, sl.hv_sst, sl.dv_sst, sl.out_ns, hipMemcpyDeviceToHost, sl.st[0]));
   return LB_OK;
 }
 
@@ -1246,10 +1229,9 @@ int finish_slot(lb_ctx* ctx, Slot& sl) {
   ts.batch_sigs_success = sl.h_stats[1];
   ts.wall_ms = ctx->wall_ms;
   if (sl.out_valid) {
-    const size_t a = (sl.out_nr + 255) & ~(size_t)255;
-    memcpy(sl.out_valid, sl.h_out, sl.out_nr);
-    memcpy(sl.out_err, sl.h_out + a, sl.out_nr);
-    if (sl.out_sst && sl.out_ns) memcpy(sl.out_sst, sl.h_out + 2 * a, sl.out_ns);
+    memcpy(sl.out_valid, sl.hv_valid, sl.out_nr);
+    memcpy(sl.out_err, sl.hv_err, sl.out_nr);
+    if (sl.out_sst && sl.out_ns) memcpy(sl.out_sst, sl.hv_sst, sl.out_ns);
     sl.out_valid = sl.out_err = sl.out_sst = nullptr;
   }
   release_borrowed(sl);
@@ -1626,8 +1608,11 @@ static int create_ctx(int device, lb_ctx** out_ctx, bool lane) {
   // 0.9-1.5 s, profiles/r05/node_q/)
   if (ok && ctx->cfg.lp_max_sets) {
     Slot& pl = ctx->slots[ctx->n_slots];
-    const size_t ns = ctx->cfg.lp_max_sets, in = ns * (32 + 192 + 16 + 16 * 96) + 65536, out = 3 * ns + 4096;
-    ok = ensure_pin(ctx, pl, in + out) == LB_OK && ensure_ws(ctx, pl, in + out + pipeline_ws_bytes(ctx, ns, ns)) == LB_OK;
+    const size_t ns = ctx->cfg.lp_max_sets;  // (16 keys a set, uncompressed signatures, every set a request)
+    const HostCallShape shape{ns, ns, 16 * ns, 192 * ns, 0, true, false};
+    const size_t io = layout_host_call(shape).end;
+    ok = ensure_pin(ctx, pl, io) == LB_OK &&
+         ensure_ws(ctx, pl, io + pipeline_ws_bytes(ctx, (uint32_t)ns, (uint32_t)ns)) == LB_OK;
   }
   if (!ok) {
     lb_destroy(ctx);
@@ -1832,7 +1817,7 @@ static int submit_device(lb_ctx* ctx, Slot& sl, const lb_request_batch* b, uint8
   pick_streams(ctx, sl);
   if (!partial) borrow_idle_stream(ctx, sl);  // (a pending two-phase call never holds a lent slot)
   LB_TRY(ensure_ws(ctx, sl, pipeline_ws_bytes(ctx, b->n_requests, b->n_sets)));
-  Bump ws{sl.d_ws, 0, sl.ws_cap};
+  Slab ws{sl.d_ws, 0, sl.ws_cap};
   LB_TRY(begin_call(ctx, sl));
   if (b->n_requests)
     LB_TRY(run_pipeline(ctx, sl, b->n_requests, b->n_sets, b->request_offsets, b->pubkeys, b->pk_offsets,
@@ -1919,69 +1904,42 @@ static int submit_host(lb_ctx* ctx, Slot& sl, const lb_request_batch* b, uint8_t
       const uint32_t j = b->pubkey_indices[k];
       if ((j & LB_PK_ROW_FLAG) && (size_t)(j & LB_PK_ROW_MASK) + 1 > n_rows) n_rows = (j & LB_PK_ROW_MASK) + 1;
     }
-  const size_t sig_bytes = b->sig_offsets[ns];
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t sz_req = sizeof(uint32_t) * (nr + 1), sz_pko = pk_off ? sizeof(uint32_t) * (ns + 1) : 0,
-               sz_pk = n_pk * (by_index ? sizeof(uint32_t) : 96), sz_msg = (size_t)ns * 32,
-               sz_sigo = sizeof(uint32_t) * (ns + 1), sz_sig = sig_bytes, sz_seed = 32, sz_rows = n_rows * 96;
-  const size_t in_bytes =
-      al(sz_req) + al(sz_pko) + al(sz_pk) + al(sz_msg) + al(sz_sigo) + al(sz_sig) + al(sz_seed) + al(sz_rows);
-  const size_t out_bytes = al(nr ? nr : 1) * 2 + al(ns ? ns : 1);
+  // the package's arrays, declared once (layout_host_call): staged, copied and bound by HostBuf
+  const HostCallShape shape{nr, ns, n_pk, b->sig_offsets[ns], n_rows, pk_off != nullptr, by_index};
+  const HostCallLayout lay = layout_host_call(shape);
+  const void* const src[HB_INPUTS] = {b->request_offsets, pk_off,
+                                      by_index ? (const void*)b->pubkey_indices : (const void*)b->pubkeys,
+                                      b->messages, b->sig_offsets, b->signatures, b->seed, b->pubkeys};
   LB_TRY(finish_slot(ctx, sl));
   pick_streams(ctx, sl);
   t_finish = ms_since(t0);
   if (!partial) borrow_idle_stream(ctx, sl);
-  LB_TRY(ensure_pin(ctx, sl, in_bytes + out_bytes));
-  LB_TRY(ensure_ws(ctx, sl, in_bytes + out_bytes + pipeline_ws_bytes(ctx, nr, ns)));
-  Bump ws{sl.d_ws, 0, sl.ws_cap};
-  char* h = sl.h_pin;
-  size_t ho = 0;
-  auto stage = [&](const void* src, size_t n) {
-    if (n) memcpy(h + ho, src, n);
-    ho += al(n);
-  };
-  stage(b->request_offsets, sz_req);
-  if (pk_off) stage(pk_off, sz_pko);
-  stage(by_index ? (const void*)b->pubkey_indices : (const void*)b->pubkeys, sz_pk);
-  stage(b->messages, sz_msg);
-  stage(b->sig_offsets, sz_sigo);
-  stage(b->signatures, sz_sig);
-  stage(b->seed, sz_seed);
-  if (n_rows) stage(b->pubkeys, sz_rows);
+  LB_TRY(ensure_pin(ctx, sl, lay.end));
+  LB_TRY(ensure_ws(ctx, sl, lay.end + pipeline_ws_bytes(ctx, nr, ns)));
+  Slab ws{sl.d_ws, lay.end, sl.ws_cap};
+  char *h = sl.h_pin, *d = sl.d_ws;
+  for (int i = 0; i < HB_INPUTS; i++)
+    if (lay.size[i]) memcpy(h + lay.off[i], src[i], lay.size[i]);
   t_stage = ms_since(t0);
-  char* d_in = ws.take<char>(in_bytes);
-  uint8_t* d_valid = ws.take<uint8_t>(nr ? nr : 1);
-  uint8_t* d_err = ws.take<uint8_t>(nr ? nr : 1);
-  uint8_t* d_sst = ws.take<uint8_t>(ns ? ns : 1);
   LB_TRY(begin_call(ctx, sl));
-  sl.dv_valid = d_valid;
-  sl.dv_err = d_err;
-  sl.dv_sst = d_sst;
-  sl.h_out = h + in_bytes;
+  sl.dv_valid = slab_at<uint8_t>(d, lay.off[HB_VALID]);
+  sl.dv_err = slab_at<uint8_t>(d, lay.off[HB_ERR]);
+  sl.dv_sst = slab_at<uint8_t>(d, lay.off[HB_SST]);
+  sl.hv_valid = slab_at<uint8_t>(h, lay.off[HB_VALID]);
+  sl.hv_err = slab_at<uint8_t>(h, lay.off[HB_ERR]);
+  sl.hv_sst = slab_at<uint8_t>(h, lay.off[HB_SST]);
   sl.out_valid = out_valid;
   sl.out_err = out_req_err;
   sl.out_sst = out_set_status;
   sl.out_nr = nr;
   sl.out_ns = out_set_status ? ns : 0;
-  LB_TRY(slot_copy(ctx, sl, d_in, h, in_bytes, hipMemcpyHostToDevice, sl.st[0]));
-  size_t o = 0;
-  auto dptr = [&](size_t n) {
-    char* p = d_in + o;
-    o += al(n);
-    return p;
-  };
-  const uint32_t* d_req = (const uint32_t*)dptr(sz_req);
-  const uint32_t* d_pko = pk_off ? (const uint32_t*)dptr(sz_pko) : nullptr;
-  const uint8_t* d_pks = (const uint8_t*)dptr(sz_pk);
-  const uint8_t* d_msg = (const uint8_t*)dptr(sz_msg);
-  const uint32_t* d_sigo = (const uint32_t*)dptr(sz_sigo);
-  const uint8_t* d_sig = (const uint8_t*)dptr(sz_sig);
-  const uint8_t* d_seed = (const uint8_t*)dptr(sz_seed);
-  const uint8_t* d_rows = n_rows ? (const uint8_t*)dptr(sz_rows) : nullptr;
+  LB_TRY(slot_copy(ctx, sl, d, h, lay.in_bytes, hipMemcpyHostToDevice, sl.st[0]));
+  const auto in8 = [&](HostBuf i) { return slab_at<const uint8_t>(d, lay.off[i]); };
+  const auto in32 = [&](HostBuf i) { return slab_at<const uint32_t>(d, lay.off[i]); };
   if (nr) {
-    LB_TRY(run_pipeline(ctx, sl, nr, ns, d_req, by_index ? d_rows : d_pks, d_pko,
-                        by_index ? (const uint32_t*)d_pks : nullptr, d_msg, d_sig, d_sigo, d_seed, d_valid, d_err, d_sst,
-                        ws, partial));
+    LB_TRY(run_pipeline(ctx, sl, nr, ns, in32(HB_REQ), by_index ? in8(HB_ROWS) : in8(HB_PK), in32(HB_PKO),
+                        by_index ? in32(HB_PK) : nullptr, in8(HB_MSG), in8(HB_SIG), in32(HB_SIGO), in8(HB_SEED),
+                        sl.dv_valid, sl.dv_err, sl.dv_sst, ws, partial));
     t_pipe = ms_since(t0);
   } else if (partial) {
     memset(sl.h_partial, 0, LB_GT_BYTES);
@@ -2346,29 +2304,49 @@ int lb_verify_requests_priority_async(lb_ctx* ctx, const lb_request_batch* b, ui
   return submit_host(ctx, ctx->prio(), b, out_valid, out_req_err, out_set_status, false, out_ticket);
 }
 // ---- helpers for small host-buffer calls ----------------------------------
-static int upload(lb_ctx* ctx, Bump& ws, const void* src, size_t n, void** out) {
-  char* d = ws.take<char>(n ? n : 1);
-  if (n) LB_HIP(hipMemcpyAsync(d, src, n, hipMemcpyHostToDevice, ctx->stream));
-  *out = d;
-  return LB_OK;
-}
+// A synchronous helper call on the idle slot 0: the call declares its buffers (bls_carve.h),
+// begin() selects the device, retires the calls in flight, sizes and carves slot 0's slab from
+// the list and uploads the inputs on ctx->stream; the call launches; end() downloads the
+// outputs and synchronises once.
+struct HelperCall : Carve<16> {
+  lb_ctx* ctx;
+  explicit HelperCall(lb_ctx* c) : ctx(c) {}
+  int begin() {
+    LB_HIP(hipSetDevice(ctx->device));
+    LB_TRY(helper_slot(ctx));
+    LB_TRY(ensure_ws(ctx, layout()));
+    Slot& sl = ctx->slots[0];
+    if (!fits(sl.ws_cap)) {
+      ctx->err = "workspace overflow";
+      return LB_ERR_OUT_OF_MEMORY;
+    }
+    bind(sl.d_ws);
+    for (int i = 0; i < n; i++)
+      if (buf[i].kind == CARVE_IN && buf[i].bytes && buf[i].src)
+        LB_HIP(hipMemcpyAsync(sl.d_ws + buf[i].off, buf[i].src, buf[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+    return LB_OK;
+  }
+  int end() {
+    const Slot& sl = ctx->slots[0];
+    for (int i = 0; i < n; i++)
+      if (buf[i].kind == CARVE_OUT && buf[i].bytes && buf[i].dst)
+        LB_HIP(hipMemcpyAsync(buf[i].dst, sl.d_ws + buf[i].off, buf[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+    LB_HIP(hipStreamSynchronize(ctx->stream));
+    return LB_OK;
+  }
+};
 
 int lb_hash_to_g2(lb_ctx* ctx, uint32_t n, const uint8_t* messages, uint8_t* out192) {
   if (!ctx || (n && (!messages || !out192))) return LB_ERR_INVALID_ARGUMENT;
   if (n == 0) return LB_OK;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  LB_TRY(ensure_ws(ctx, (size_t)n * (32 + sizeof(g2a) + 192) + 4096));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void* d_msg;
-  LB_TRY(upload(ctx, ws, messages, (size_t)n * 32, &d_msg));
-  g2a* d_h = ws.take<g2a>(n);
-  uint8_t* d_out = ws.take<uint8_t>((size_t)n * 192);
-  LB_LAUNCH(k_hash, blocks_for(n), TPB, n, (const uint8_t*)d_msg, d_h);
+  HelperCall c(ctx);
+  auto d_msg = c.in(messages, (size_t)n * 32);
+  auto d_h = c.scratch<g2a>(n);
+  auto d_out = c.out(out192, (size_t)n * 192);
+  LB_TRY(c.begin());
+  LB_LAUNCH(k_hash, blocks_for(n), TPB, n, d_msg, d_h);
   LB_LAUNCH(k_g2a_serialize, blocks_for(n), TPB, n, (const g2a*)d_h, d_out);
-  LB_HIP(hipMemcpyAsync(out192, d_out, (size_t)n * 192, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  return LB_OK;
+  return c.end();
 }
 
 int lb_decode_signatures(lb_ctx* ctx, uint32_t n, const uint8_t* sigs, const uint32_t* sig_off, uint8_t* out_status,
@@ -2377,23 +2355,38 @@ int lb_decode_signatures(lb_ctx* ctx, uint32_t n, const uint8_t* sigs, const uin
   if (n == 0) return LB_OK;
   for (uint32_t i = 0; i < n; i++)
     if (sig_off[i + 1] < sig_off[i]) return LB_ERR_INVALID_ARGUMENT;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  const size_t nb = sig_off[n];
-  LB_TRY(ensure_ws(ctx, nb + (size_t)n * (4 + sizeof(g2j) + 1 + 192) + 8192));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void *d_s, *d_o;
-  LB_TRY(upload(ctx, ws, sigs, nb, &d_s));
-  LB_TRY(upload(ctx, ws, sig_off, sizeof(uint32_t) * (n + 1), &d_o));
-  g2j* d_sig = ws.take<g2j>(n);
-  uint8_t* d_st = ws.take<uint8_t>(n);
-  uint8_t* d_out = ws.take<uint8_t>((size_t)n * 192);
-  LB_LAUNCH(k_decode_sigs, blocks_for(n), TPB, n, (const uint8_t*)d_s, (const uint32_t*)d_o, (const uint8_t*)nullptr,
-            d_sig, d_st);
+  HelperCall c(ctx);
+  auto d_s = c.in(sigs, sig_off[n]);
+  auto d_o = c.in(sig_off, (size_t)n + 1);
+  auto d_sig = c.scratch<g2j>(n);
+  auto d_st = c.out(out_status, n);
+  auto d_out = c.out(out192, (size_t)n * 192);  // (out192 is optional: serialized all the same)
+  LB_TRY(c.begin());
+  LB_LAUNCH(k_decode_sigs, blocks_for(n), TPB, n, d_s, d_o, (const uint8_t*)nullptr, d_sig, d_st);
   LB_LAUNCH(k_g2_serialize, blocks_for(n), TPB, n, (const g2j*)d_sig, d_out);
-  LB_HIP(hipMemcpyAsync(out_status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
-  if (out192) LB_HIP(hipMemcpyAsync(out192, d_out, (size_t)n * 192, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
+  return c.end();
+}
+
+// One aggregated key from `src` (n keys by bytes or by table index): Jacobian sum, serialized
+static int aggregate_pubkeys(lb_ctx* ctx, uint32_t n, const uint8_t* pks, const uint32_t* indices, uint8_t* out96,
+                             uint8_t* out_status) {
+  HelperCall c(ctx);
+  const uint32_t off[2] = {0, n};
+  uint8_t st = 0;
+  auto d_p = c.in(pks, (size_t)n * 96, pks != nullptr);
+  auto d_idx = c.in(indices, n, indices != nullptr);
+  auto d_off = c.in(off, 2);
+  auto d_pk = c.scratch<g1j>(1);
+  auto d_out = c.out(out96, 96);
+  auto d_st = c.out(&st, 1);
+  LB_TRY(c.begin());
+  const PkSource src{d_p, d_idx, indices ? ctx->d_table : nullptr, indices ? ctx->table_n : 0};
+  LB_LAUNCH(k_pubkeys_single, 1, TPB, 1u, src, d_off, d_pk, d_st);
+  LB_LAUNCH(k_pubkeys_agg, 1, TPB, 1u, src, d_off, d_pk, d_st);
+  LB_LAUNCH(k_g1_serialize, 1, TPB, 1u, (const g1j*)d_pk, d_out);
+  LB_TRY(c.end());
+  if (st == LB_ST_PK_INFINITY) st = LB_ST_OK;  // an infinite aggregate is a valid encoding (0x40...)
+  if (out_status) *out_status = st;
   return LB_OK;
 }
 
@@ -2403,48 +2396,20 @@ int lb_aggregate_pubkeys(lb_ctx* ctx, uint32_t n, const uint8_t* pks, uint8_t* o
     ctx->err = "EMPTY_AGGREGATE_ARRAY";
     return LB_ERR_INVALID_ARGUMENT;
   }
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  LB_TRY(ensure_ws(ctx, (size_t)n * 96 + 8192));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void* d_p;
-  LB_TRY(upload(ctx, ws, pks, (size_t)n * 96, &d_p));
-  uint32_t off[2] = {0, n};
-  void* d_off;
-  LB_TRY(upload(ctx, ws, off, sizeof(off), &d_off));
-  g1j* d_pk = ws.take<g1j>(1);
-  uint8_t* d_st = ws.take<uint8_t>(1);
-  uint8_t* d_out = ws.take<uint8_t>(96);
-  const PkSource src{(const uint8_t*)d_p, nullptr, nullptr, 0};
-  LB_LAUNCH(k_pubkeys_single, 1, TPB, 1u, src, (const uint32_t*)d_off, d_pk, d_st);
-  LB_LAUNCH(k_pubkeys_agg, 1, TPB, 1u, src, (const uint32_t*)d_off, d_pk, d_st);
-  LB_LAUNCH(k_g1_serialize, 1, TPB, 1u, (const g1j*)d_pk, d_out);
-  uint8_t st = 0;
-  LB_HIP(hipMemcpyAsync(out96, d_out, 96, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipMemcpyAsync(&st, d_st, 1, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  if (st == LB_ST_PK_INFINITY) st = LB_ST_OK;  // an infinite aggregate is a valid encoding (0x40...)
-  if (out_status) *out_status = st;
-  return LB_OK;
+  return aggregate_pubkeys(ctx, n, pks, nullptr, out96, out_status);
 }
 
 int lb_pubkeys_from_bytes(lb_ctx* ctx, uint32_t n, const uint8_t* pks, uint32_t pk_len, uint8_t* out96,
                           uint8_t* out_status) {
   if (!ctx || (n && (!pks || !out96 || !out_status)) || (pk_len != 48 && pk_len != 96)) return LB_ERR_INVALID_ARGUMENT;
   if (n == 0) return LB_OK;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  LB_TRY(ensure_ws(ctx, (size_t)n * (pk_len + 96 + 1) + 8192));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void* d_in;
-  LB_TRY(upload(ctx, ws, pks, (size_t)n * pk_len, &d_in));
-  uint8_t* d_out = ws.take<uint8_t>((size_t)n * 96);
-  uint8_t* d_st = ws.take<uint8_t>(n);
-  LB_LAUNCH(k_pubkey_validate, blocks_for(n), TPB, n, (const uint8_t*)d_in, pk_len, d_out, d_st);
-  LB_HIP(hipMemcpyAsync(out96, d_out, (size_t)n * 96, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipMemcpyAsync(out_status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  return LB_OK;
+  HelperCall c(ctx);
+  auto d_in = c.in(pks, (size_t)n * pk_len);
+  auto d_out = c.out(out96, (size_t)n * 96);
+  auto d_st = c.out(out_status, n);
+  LB_TRY(c.begin());
+  LB_LAUNCH(k_pubkey_validate, blocks_for(n), TPB, n, d_in, pk_len, d_out, d_st);
+  return c.end();
 }
 
 // ---- device-resident pubkey table (index2pubkey mirror) ------------------------
@@ -2482,16 +2447,13 @@ int lb_pubkey_table_append(lb_ctx* ctx, uint32_t n, const uint8_t* pks, uint32_t
   std::vector<uint8_t> st;
   for (uint32_t first = 0; first < n; first += chunk) {
     const uint32_t m = n - first < chunk ? n - first : chunk;
-    LB_TRY(ensure_ws(ctx, (size_t)m * (pk_len + 1) + 4096));
-    Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-    void* d_in;
-    LB_TRY(upload(ctx, ws, pks + (size_t)first * pk_len, (size_t)m * pk_len, &d_in));
-    uint8_t* d_st = ws.take<uint8_t>(m);
-    LB_LAUNCH(k_table_decode, blocks_for(m), TPB, m, (const uint8_t*)d_in, pk_len, ctx->d_table + ctx->table_n + first,
-              d_st);
     st.resize(m);
-    LB_HIP(hipMemcpyAsync(st.data(), d_st, m, hipMemcpyDeviceToHost, ctx->stream));
-    LB_HIP(hipStreamSynchronize(ctx->stream));
+    HelperCall c(ctx);
+    auto d_in = c.in(pks + (size_t)first * pk_len, (size_t)m * pk_len);
+    auto d_st = c.out(st.data(), m);
+    LB_TRY(c.begin());
+    LB_LAUNCH(k_table_decode, blocks_for(m), TPB, m, d_in, pk_len, ctx->d_table + ctx->table_n + first, d_st);
+    LB_TRY(c.end());
     for (uint32_t i = 0; i < m; i++)
       if (st[i] != LB_ST_OK) {
         if (out_bad_index) *out_bad_index = (int32_t)(first + i);
@@ -2520,15 +2482,11 @@ int lb_pubkey_table_truncate(lb_ctx* ctx, uint32_t n) {
 int lb_pubkey_table_read(lb_ctx* ctx, uint32_t first, uint32_t n, uint8_t* out96) {
   if (!ctx || (n && !out96) || (uint64_t)first + n > ctx->table_n) return LB_ERR_INVALID_ARGUMENT;
   if (n == 0) return LB_OK;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  LB_TRY(ensure_ws(ctx, (size_t)n * 96 + 4096));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  uint8_t* d_out = ws.take<uint8_t>((size_t)n * 96);
+  HelperCall c(ctx);
+  auto d_out = c.out(out96, (size_t)n * 96);
+  LB_TRY(c.begin());
   LB_LAUNCH(k_g1a_serialize, blocks_for(n), TPB, n, (const g1a*)(ctx->d_table + first), d_out);
-  LB_HIP(hipMemcpyAsync(out96, d_out, (size_t)n * 96, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  return LB_OK;
+  return c.end();
 }
 
 int lb_aggregate_pubkeys_indexed(lb_ctx* ctx, uint32_t n, const uint32_t* indices, uint8_t* out96,
@@ -2538,29 +2496,7 @@ int lb_aggregate_pubkeys_indexed(lb_ctx* ctx, uint32_t n, const uint32_t* indice
     ctx->err = "EMPTY_AGGREGATE_ARRAY";
     return LB_ERR_INVALID_ARGUMENT;
   }
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  LB_TRY(ensure_ws(ctx, (size_t)n * 4 + 8192));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void* d_idx;
-  LB_TRY(upload(ctx, ws, indices, (size_t)n * 4, &d_idx));
-  uint32_t off[2] = {0, n};
-  void* d_off;
-  LB_TRY(upload(ctx, ws, off, sizeof(off), &d_off));
-  g1j* d_pk = ws.take<g1j>(1);
-  uint8_t* d_st = ws.take<uint8_t>(1);
-  uint8_t* d_out = ws.take<uint8_t>(96);
-  const PkSource src{nullptr, (const uint32_t*)d_idx, ctx->d_table, ctx->table_n};
-  LB_LAUNCH(k_pubkeys_single, 1, TPB, 1u, src, (const uint32_t*)d_off, d_pk, d_st);
-  LB_LAUNCH(k_pubkeys_agg, 1, TPB, 1u, src, (const uint32_t*)d_off, d_pk, d_st);
-  LB_LAUNCH(k_g1_serialize, 1, TPB, 1u, (const g1j*)d_pk, d_out);
-  uint8_t st = 0;
-  LB_HIP(hipMemcpyAsync(out96, d_out, 96, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipMemcpyAsync(&st, d_st, 1, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  if (st == LB_ST_PK_INFINITY) st = LB_ST_OK;  // an infinite aggregate is a valid encoding (0x40...)
-  if (out_status) *out_status = st;
-  return LB_OK;
+  return aggregate_pubkeys(ctx, n, nullptr, indices, out96, out_status);
 }
 
 // ---- signing roots -----------------------------------------------------------
@@ -2568,23 +2504,16 @@ static int signing_roots(lb_ctx* ctx, uint32_t n, uint32_t m, const uint8_t* in,
                          const uint8_t* domains, uint32_t dstride, uint8_t* out32) {
   if (!ctx || (n && (!in || !domains || !out32)) || (dstride != 0 && dstride != 32)) return LB_ERR_INVALID_ARGUMENT;
   if (n == 0) return LB_OK;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  const size_t n_dom = dstride ? n : 1;
-  LB_TRY(ensure_ws(ctx, (size_t)n * (in_per_obj + 32) + n_dom * 32 + 8192));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void *d_in, *d_dom;
-  LB_TRY(upload(ctx, ws, in, (size_t)n * in_per_obj, &d_in));
-  LB_TRY(upload(ctx, ws, domains, n_dom * 32, &d_dom));
-  uint8_t* d_out = ws.take<uint8_t>((size_t)n * 32);
+  HelperCall c(ctx);
+  auto d_in = c.in(in, (size_t)n * in_per_obj);
+  auto d_dom = c.in(domains, (dstride ? (size_t)n : 1) * 32);
+  auto d_out = c.out(out32, (size_t)n * 32);
+  LB_TRY(c.begin());
   if (m == 0)
-    LB_LAUNCH(k_signing_root_att, blocks_for(n), TPB, n, (const uint8_t*)d_in, (const uint8_t*)d_dom, dstride, d_out);
+    LB_LAUNCH(k_signing_root_att, blocks_for(n), TPB, n, d_in, d_dom, dstride, d_out);
   else
-    LB_LAUNCH(k_signing_root_chunks, blocks_for(n), TPB, n, m, (const uint8_t*)d_in, (const uint8_t*)d_dom, dstride,
-              d_out);
-  LB_HIP(hipMemcpyAsync(out32, d_out, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  return LB_OK;
+    LB_LAUNCH(k_signing_root_chunks, blocks_for(n), TPB, n, m, d_in, d_dom, dstride, d_out);
+  return c.end();
 }
 
 int lb_signing_roots_attestation(lb_ctx* ctx, uint32_t n, const uint8_t* data128, const uint8_t* domains,
@@ -2619,26 +2548,19 @@ int lb_aggregate_signatures(lb_ctx* ctx, uint32_t n, const uint8_t* sigs, const 
   }
   for (uint32_t i = 0; i < n; i++)
     if (sig_off[i + 1] < sig_off[i]) return LB_ERR_INVALID_ARGUMENT;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  const size_t nb = sig_off[n];
-  LB_TRY(ensure_ws(ctx, nb + (size_t)n * (4 + sizeof(g2j) + 1) + 8192));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void *d_s, *d_o;
-  LB_TRY(upload(ctx, ws, sigs, nb, &d_s));
-  LB_TRY(upload(ctx, ws, sig_off, sizeof(uint32_t) * (n + 1), &d_o));
-  g2j* d_sig = ws.take<g2j>(n);
-  uint8_t* d_st = ws.take<uint8_t>(n);
-  g2j* d_sum = ws.take<g2j>(1);
-  uint8_t* d_out = ws.take<uint8_t>(192);
-  LB_LAUNCH(k_decode_sigs, blocks_for(n), TPB, n, (const uint8_t*)d_s, (const uint32_t*)d_o, (const uint8_t*)nullptr,
-            d_sig, d_st);
+  std::vector<uint8_t> st(n);
+  HelperCall c(ctx);
+  auto d_s = c.in(sigs, sig_off[n]);
+  auto d_o = c.in(sig_off, (size_t)n + 1);
+  auto d_sig = c.scratch<g2j>(n);
+  auto d_st = c.out(st.data(), n);
+  auto d_sum = c.scratch<g2j>(1);
+  auto d_out = c.out(out192, 192);
+  LB_TRY(c.begin());
+  LB_LAUNCH(k_decode_sigs, blocks_for(n), TPB, n, d_s, d_o, (const uint8_t*)nullptr, d_sig, d_st);
   LB_LAUNCH(k_jac_sum<fp2>, 1, 256, n, (const g2j*)d_sig, d_sum);
   LB_LAUNCH(k_g2_serialize, 1, TPB, 1u, (const g2j*)d_sum, d_out);
-  std::vector<uint8_t> st(n);
-  LB_HIP(hipMemcpyAsync(st.data(), d_st, n, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipMemcpyAsync(out192, d_out, 192, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
+  LB_TRY(c.end());
   *out_bad_index = -1;
   for (uint32_t i = 0; i < n; i++)
     if (st[i] != LB_ST_OK) {
@@ -2715,36 +2637,20 @@ int sm_validate(lb_ctx* ctx, const lb_same_message_batch* b) {
   return LB_OK;
 }
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+// A buffer of the same-message package on slot `sl`: offset `off` (SmLayout, bls_carve.h) of
+// the slot's slab / of its pinned staging; nullptr for a buffer the package does not have
+template <class T>
+T* sm_d(const Slot& sl, size_t off) { return slab_at<T>(sl.d_ws, off); }
+template <class T>
+T* sm_h(const Slot& sl, size_t off) { return slab_at<T>(sl.h_pin, off); }
 
-// phase-2 device reserve: the retry pipeline over at most every set, its gathered inputs
-size_t sm_phase2_bytes(const lb_ctx* ctx, uint32_t ns) {
-  const size_t n = ns ? ns : 1;
-  return pipeline_ws_bytes(ctx, ns, ns) + n * (2 * 4 + sizeof(g2j) + 1 + 32 + 4 + 4 + 2) + 16 * 256;
-}
-
-// What the front of phase 1 (sm_front: staging, upload, decode, aggregation) leaves for the
-// verification of the aggregated sets (sm_submit) or for lb_same_message_aggregates.
-struct SmFront {
-  bool by_index = false;
-  size_t in_bytes = 0, res_bytes = 0;
-  char* h = nullptr;  // the slot's pinned staging: inputs, then results
-  const uint32_t* h_joff = nullptr;
-  const uint8_t *d_pks = nullptr, *d_msgs = nullptr, *d_seed = nullptr, *d_rows = nullptr;
-  const uint32_t *d_areq = nullptr, *d_asig = nullptr, *d_joff = nullptr;
-  g2j* d_sig = nullptr;
-  uint8_t *d_sst = nullptr, *d_jpkst = nullptr, *d_pk96 = nullptr, *d_sig192 = nullptr, *d_jbad = nullptr;
-};
-
-// The front of phase 1 on slot `sl` (already retired by the caller), in aggregation mode `mode`:
-// the package staged and uploaded, every signature decoded + validated once, each job's
-// aggregated set in d_pk96 / d_sig192 with its flags d_jbad / d_jpkst.  pin_extra / ws_extra:
-// what the caller needs of the slot's staging and workspace after it (ws: the bump after it).
-int sm_front(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint32_t mode, size_t pin_extra, size_t ws_extra,
-             Bump& ws, SmFront& f) {
+// The package's shape and its layout, and the slot's staging and slab sized for all of it --
+// both phases, every set retried -- before anything is enqueued: nothing later can fail for
+// space.  front_only: lb_same_message_aggregates (no verification, no phase 2).
+int sm_prepare(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, bool agg, bool front_only, SmShape& s,
+               SmLayout& L) {
   const uint32_t nj = b->n_jobs, ns = b->n_sets;
   const bool by_index = b->pubkey_indices != nullptr;
-  const bool randomized = mode == LB_SM_RANDOMIZED;
   // mixed package (indices AND rows): rows of `pubkeys` named by flagged indices, as in
   // lb_request_batch (every row < n_rows is staged)
   size_t n_rows = 0;
@@ -2753,89 +2659,69 @@ int sm_front(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint32_t mod
       const uint32_t j = b->pubkey_indices[i];
       if ((j & LB_PK_ROW_FLAG) && (size_t)(j & LB_PK_ROW_MASK) + 1 > n_rows) n_rows = (j & LB_PK_ROW_MASK) + 1;
     }
-  const size_t sz_joff = sizeof(uint32_t) * (nj + 1), sz_pk = (size_t)ns * (by_index ? 4 : 96),
-               sz_sigo = sizeof(uint32_t) * (ns + 1), sz_sig = b->sig_offsets[ns], sz_msg = (size_t)nj * 32,
-               sz_seed = 32, sz_areq = sizeof(uint32_t) * (nj + 1), sz_asig = sizeof(uint32_t) * (nj + 1),
-               sz_rows = n_rows * 96;
-  const size_t in_bytes = al256(sz_joff) + al256(sz_pk) + al256(sz_sigo) + al256(sz_sig) + al256(sz_msg) +
-                          al256(sz_seed) + al256(sz_areq) + al256(sz_asig) + al256(sz_rows);
-  const size_t ns1 = ns ? ns : 1;
-  const size_t res_bytes = 4 * al256(nj);
-  const size_t extra = ns1 * (sizeof(g2j) + 1) + (size_t)nj * (sizeof(g1j) + 1 + 96 + 192 + 1 + 2) + 16 * 256;
-  LB_TRY(ensure_pin(ctx, sl, in_bytes + res_bytes + pin_extra));
-  // (+ a small package's decode records: 4 + 2 records, 5 flags and a status per signature)
-  const size_t dec_bytes = ns <= LB_SM_DEC_MAX ? (size_t)ns * (6 * 64 + 5 * 4 + 1) + 6 * 256 : 0;
-  LB_TRY(ensure_ws(ctx, sl, in_bytes + extra + ws_extra + dec_bytes));
-  ws = Bump{sl.d_ws, 0, sl.ws_cap};
-  char* h = sl.h_pin;
-  size_t ho = 0;
-  auto stage = [&](const void* src, size_t n) {
-    char* p = h + ho;
-    if (n && src) memcpy(p, src, n);
-    ho += al256(n);
-    return p;
-  };
-  const uint32_t* h_joff = (const uint32_t*)stage(b->job_offsets, sz_joff);
-  stage(by_index ? (const void*)b->pubkey_indices : (const void*)b->pubkeys, sz_pk);
-  stage(b->sig_offsets, sz_sigo);
-  stage(b->signatures, sz_sig);
-  stage(b->messages, sz_msg);
-  stage(b->seed, sz_seed);
-  uint32_t* areq = (uint32_t*)stage(nullptr, sz_areq);
-  uint32_t* asig = (uint32_t*)stage(nullptr, sz_asig);
-  if (n_rows) stage(b->pubkeys, sz_rows);
+  s = SmShape{nj, ns, b->sig_offsets[ns], n_rows, by_index, agg, ns && ns <= LB_SM_DEC_MAX && ctx->sm_lp_decode, front_only,
+              front_only ? 0 : pipeline_ws_bytes(ctx, nj, nj), front_only ? 0 : pipeline_ws_bytes(ctx, ns, ns)};
+  L = layout_same_message(s, ns);
+  LB_TRY(ensure_pin(ctx, sl, L.pin_end));
+  LB_TRY(ensure_ws(ctx, sl, L.ws_end));
+  if (L.ws_end > sl.ws_cap || L.pin_end > sl.pin_cap) {
+    ctx->err = "workspace overflow";
+    return LB_ERR_OUT_OF_MEMORY;
+  }
+  return LB_OK;
+}
+
+// The front of phase 1 on slot `sl` (already retired by the caller, sized by sm_prepare), in
+// aggregation mode `mode`: the package staged and uploaded, every signature decoded + validated
+// once, each job's aggregated set in d_pk96 / d_sig192 with its flags d_jbad / d_jpkst.
+int sm_front(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint32_t mode, const SmShape& s,
+             const SmLayout& L) {
+  const uint32_t nj = b->n_jobs, ns = b->n_sets;
+  const bool by_index = s.by_index;
+  const bool randomized = mode == LB_SM_RANDOMIZED;
+  const void* const src[SI_COUNT] = {b->job_offsets, by_index ? (const void*)b->pubkey_indices : (const void*)b->pubkeys,
+                                     b->sig_offsets, b->signatures, b->messages, b->seed, nullptr, nullptr, b->pubkeys};
+  for (int i = 0; i < SI_COUNT; i++)
+    if (L.in_size[i] && src[i]) memcpy(sl.h_pin + L.in[i], src[i], L.in_size[i]);
+  uint32_t *areq = sm_h<uint32_t>(sl, L.in[SI_AREQ]), *asig = sm_h<uint32_t>(sl, L.in[SI_ASIG]);
   for (uint32_t j = 0; j <= nj; j++) {
     areq[j] = j;        // every job one request of one (aggregated) set
     asig[j] = 192 * j;  // Signature.aggregate(...).toBytes(uncompressed)
   }
-  char* d_in = ws.take<char>(in_bytes);
-  size_t o = 0;
-  auto dptr = [&](size_t n) {
-    char* p = d_in + o;
-    o += al256(n);
-    return p;
-  };
-  const uint32_t* d_joff = (const uint32_t*)dptr(sz_joff);
-  const uint8_t* d_pks = (const uint8_t*)dptr(sz_pk);
-  const uint32_t* d_sigo = (const uint32_t*)dptr(sz_sigo);
-  const uint8_t* d_sigs = (const uint8_t*)dptr(sz_sig);
-  const uint8_t* d_msgs = (const uint8_t*)dptr(sz_msg);
-  const uint8_t* d_seed = (const uint8_t*)dptr(sz_seed);
-  const uint32_t* d_areq = (const uint32_t*)dptr(sz_areq);
-  const uint32_t* d_asig = (const uint32_t*)dptr(sz_asig);
-  const uint8_t* d_rows = n_rows ? (const uint8_t*)dptr(sz_rows) : nullptr;
-  g2j* d_sig = ws.take<g2j>(ns1);
-  uint8_t* d_sst = ws.take<uint8_t>(ns1);
-  g1j* d_jpk = ws.take<g1j>(nj);
-  uint8_t* d_jpkst = ws.take<uint8_t>(nj);
-  uint8_t* d_pk96 = ws.take<uint8_t>((size_t)nj * 96);
-  uint8_t* d_sig192 = ws.take<uint8_t>((size_t)nj * 192);
-  uint8_t* d_jbad = ws.take<uint8_t>(nj);
+  const uint32_t* d_joff = sm_d<const uint32_t>(sl, L.in[SI_JOFF]);
+  const uint8_t* d_pks = sm_d<const uint8_t>(sl, L.in[SI_PK]);
+  const uint32_t* d_sigo = sm_d<const uint32_t>(sl, L.in[SI_SIGO]);
+  const uint8_t* d_sigs = sm_d<const uint8_t>(sl, L.in[SI_SIG]);
+  const uint8_t* d_seed = sm_d<const uint8_t>(sl, L.in[SI_SEED]);
+  const uint8_t* d_rows = sm_d<const uint8_t>(sl, L.in[SI_ROWS]);
+  g2j* d_sig = sm_d<g2j>(sl, L.d_sig);
+  uint8_t* d_sst = sm_d<uint8_t>(sl, L.d_sst);
+  g1j* d_jpk = sm_d<g1j>(sl, L.d_jpk);
+  uint8_t* d_jpkst = sm_d<uint8_t>(sl, L.d_jpkst);
+  uint8_t* d_pk96 = sm_d<uint8_t>(sl, L.d_pk96);
+  uint8_t* d_sig192 = sm_d<uint8_t>(sl, L.d_sig192);
+  uint8_t* d_jbad = sm_d<uint8_t>(sl, L.d_jbad);
   LB_TRY(begin_call(ctx, sl));
-  LB_HIP(hipMemcpyAsync(d_in, h, in_bytes, hipMemcpyHostToDevice, sl.st[0]));
-  const PkSource src{by_index ? d_rows : d_pks, by_index ? (const uint32_t*)d_pks : nullptr, ctx->d_table,
-                     ctx->table_n};
+  LB_HIP(hipMemcpyAsync(sl.d_ws, sl.h_pin, L.in_bytes, hipMemcpyHostToDevice, sl.st[0]));
+  const PkSource src_pk{by_index ? d_rows : d_pks, by_index ? (const uint32_t*)d_pks : nullptr, ctx->d_table,
+                        ctx->table_n};
   const uint32_t agg_grid = nj < 16384u ? nj : 16384u;
   // randomized sums: the G1 side needs only the upload, so with a second stream it runs there,
   // beside the decode and the G2 side (joined below, before the aggregated sets are read)
   const int pk_st = randomized && sl.st[1] != sl.st[0] ? 1 : 0;
   if (randomized) {
     if (pk_st) LB_TRY(stream_wait(ctx, sl, 0, 1, 5));
-    LB_STAGE("sm_rand_pk", pk_st, k_sm_rand_pk, agg_grid, TPB, nj, d_joff, src, d_seed, d_jpk, d_jpkst, d_pk96);
+    LB_STAGE("sm_rand_pk", pk_st, k_sm_rand_pk, agg_grid, TPB, nj, d_joff, src_pk, d_seed, d_jpk, d_jpkst, d_pk96);
   }
-  if (ns && ns <= LB_SM_DEC_MAX && ctx->sm_lp_decode) {
+  if (s.dec) {
     // a small package: each signature's decode as a round program on an 8-row workgroup (~540
     // rounds) instead of k_decode_sigs' one-lane chain (~4 ms); the same outputs and statuses
     LB_TRY(lp_ensure(ctx));
-    uint32_t* d_dec_in = ws.take<uint32_t>((size_t)ns * 4 * 16);
-    uint32_t* d_dec_fl = ws.take<uint32_t>((size_t)ns * 3);
-    uint32_t* d_dec_out = ws.take<uint32_t>((size_t)ns * 2 * 16);
-    uint32_t* d_dec_ofl = ws.take<uint32_t>((size_t)ns * 2);
-    uint8_t* d_dec_pre = ws.take<uint8_t>(ns);
-    if (ws.off > ws.cap) {
-      ctx->err = "workspace overflow";
-      return LB_ERR_OUT_OF_MEMORY;
-    }
+    uint32_t* d_dec_in = sm_d<uint32_t>(sl, L.dec_in);
+    uint32_t* d_dec_fl = sm_d<uint32_t>(sl, L.dec_fl);
+    uint32_t* d_dec_out = sm_d<uint32_t>(sl, L.dec_out);
+    uint32_t* d_dec_ofl = sm_d<uint32_t>(sl, L.dec_ofl);
+    uint8_t* d_dec_pre = sm_d<uint8_t>(sl, L.dec_pre);
     LB_STAGE("sm_decode", 0, k_sm_dec_prep, blocks_for(ns, 256), 256u, ns, d_sigs, d_sigo, d_dec_in, d_dec_fl,
              d_dec_pre);
     LB_STAGE("sm_decode", 0, k_lp_dec, ns, LB_LP_DEC_ROWS * 16u, ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_SIG_DECODE].off, ns,
@@ -2852,29 +2738,11 @@ int sm_front(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint32_t mod
              (const uint8_t*)d_sst, d_sig192, d_jbad);
     if (pk_st) LB_TRY(stream_wait(ctx, sl, 1, 0, 6));
   } else {
-    LB_STAGE("sm_pubkeys", 0, k_pubkeys_single, blocks_for(nj), TPB, nj, src, d_joff, d_jpk, d_jpkst);
-    LB_STAGE("sm_pubkeys_agg", 0, k_pubkeys_agg, agg_grid, TPB, nj, src, d_joff, d_jpk, d_jpkst);
+    LB_STAGE("sm_pubkeys", 0, k_pubkeys_single, blocks_for(nj), TPB, nj, src_pk, d_joff, d_jpk, d_jpkst);
+    LB_STAGE("sm_pubkeys_agg", 0, k_pubkeys_agg, agg_grid, TPB, nj, src_pk, d_joff, d_jpk, d_jpkst);
     LB_STAGE("sm_aggregate", 0, k_same_message_agg, agg_grid, TPB, nj, d_joff, (const g2j*)d_sig,
              (const uint8_t*)d_sst, (const g1j*)d_jpk, d_pk96, d_sig192, d_jbad);
   }
-  f.by_index = by_index;
-  f.in_bytes = in_bytes;
-  f.res_bytes = res_bytes;
-  f.h = h;
-  f.h_joff = h_joff;
-  f.d_pks = d_pks;
-  f.d_msgs = d_msgs;
-  f.d_seed = d_seed;
-  f.d_rows = d_rows;
-  f.d_areq = d_areq;
-  f.d_asig = d_asig;
-  f.d_joff = d_joff;
-  f.d_sig = d_sig;
-  f.d_sst = d_sst;
-  f.d_jpkst = d_jpkst;
-  f.d_pk96 = d_pk96;
-  f.d_sig192 = d_sig192;
-  f.d_jbad = d_jbad;
   return LB_OK;
 }
 
@@ -2895,14 +2763,16 @@ inline uint32_t job_sig_jobs_per_wg(uint32_t n_jobs, uint64_t n_sets) {
 // The stage sm_job_sig: every job's included signatures summed and compressed (k_aggsig.hip),
 // copied into the call's pinned results.
 int sm_job_sig(lb_ctx* ctx, Slot& sl, SmState& m) {
+  const SmLayout& L = m.lay;
   const uint32_t jpw = job_sig_jobs_per_wg(m.nj, m.ns);
   const uint32_t runs = (m.nj + jpw - 1) / jpw;
-  LB_STAGE("sm_job_sig", 0, k_job_sig, runs < 16384u ? runs : 16384u, TPB, m.nj, jpw, m.d_joff, m.d_sig,
-           (const uint8_t*)m.d_inc, m.d_agg96, m.d_aggcnt);
-  uint8_t* h = const_cast<uint8_t*>(m.h_agg);
-  LB_HIP(hipMemcpyAsync(h, m.d_agg96, (size_t)m.nj * 96, hipMemcpyDeviceToHost, sl.st[0]));
-  LB_HIP(hipMemcpyAsync(h + al256((size_t)m.nj * 96), m.d_aggcnt, (size_t)m.nj * 4, hipMemcpyDeviceToHost,
-                        sl.st[0]));
+  uint8_t* d_agg96 = sm_d<uint8_t>(sl, L.d_agg96);
+  uint32_t* d_aggcnt = sm_d<uint32_t>(sl, L.d_aggcnt);
+  LB_STAGE("sm_job_sig", 0, k_job_sig, runs < 16384u ? runs : 16384u, TPB, m.nj, jpw,
+           sm_d<const uint32_t>(sl, L.in[SI_JOFF]), sm_d<const g2j>(sl, L.d_sig), sm_d<const uint8_t>(sl, L.d_inc),
+           d_agg96, d_aggcnt);
+  LB_HIP(hipMemcpyAsync(sm_h<uint8_t>(sl, L.h_agg96), d_agg96, (size_t)m.nj * 96, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_HIP(hipMemcpyAsync(sm_h<uint8_t>(sl, L.h_aggcnt), d_aggcnt, (size_t)m.nj * 4, hipMemcpyDeviceToHost, sl.st[0]));
   return LB_OK;
 }
 
@@ -2912,85 +2782,48 @@ int sm_submit(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint8_t* ou
               const SmAggOut* agg = nullptr) {
   const uint32_t nj = b->n_jobs, ns = b->n_sets;
   const uint32_t mode = ctx->sm_mode;  // read once: the call keeps it whatever the context does later
-  const size_t ns1 = ns ? ns : 1;
-  const size_t retry_bytes = 2 * al256(4 * ns1) + 2 * al256(ns1);
-  // an _agg call: the mask (staged), then the jobs' signatures and counts (results), after the
-  // retry lists in the pinned area; mask, include flags and both outputs in the workspace
-  const size_t agg_pin = agg ? al256(ns1) + al256((size_t)nj * 96) + al256((size_t)nj * 4) : 0;
-  const size_t agg_ws = agg ? 2 * al256(ns1) + al256((size_t)nj * 96) + al256((size_t)nj * 4) + 4 * 256 : 0;
-  Bump ws{nullptr, 0, 0};
-  SmFront f;
-  LB_TRY(sm_front(ctx, sl, b, mode, retry_bytes + agg_pin,
-                  pipeline_ws_bytes(ctx, nj, nj) + sm_phase2_bytes(ctx, ns) + agg_ws, ws, f));
-  const bool by_index = f.by_index;
-  const size_t in_bytes = f.in_bytes, res_bytes = f.res_bytes;
-  char* h = f.h;
-  const uint32_t* h_joff = f.h_joff;
-  const uint8_t *d_pks = f.d_pks, *d_msgs = f.d_msgs, *d_seed = f.d_seed, *d_rows = f.d_rows;
-  const uint32_t *d_areq = f.d_areq, *d_asig = f.d_asig;
-  g2j* d_sig = f.d_sig;
-  uint8_t *d_sst = f.d_sst, *d_jpkst = f.d_jpkst, *d_pk96 = f.d_pk96, *d_sig192 = f.d_sig192, *d_jbad = f.d_jbad;
-  uint8_t* d_valid = ws.take<uint8_t>(nj);
-  uint8_t* d_err = ws.take<uint8_t>(nj);
   SmState& m = sl.sm;
+  LB_TRY(sm_prepare(ctx, sl, b, agg != nullptr, false, m.shape, m.lay));
+  const SmLayout& L = m.lay;
+  LB_TRY(sm_front(ctx, sl, b, mode, m.shape, L));
+  uint8_t *d_valid = sm_d<uint8_t>(sl, L.d_valid), *d_err = sm_d<uint8_t>(sl, L.d_err);
+  uint8_t *d_jbad = sm_d<uint8_t>(sl, L.d_jbad), *d_jpkst = sm_d<uint8_t>(sl, L.d_jpkst);
   m.agg = agg != nullptr;
-  char* h_res = h + in_bytes;
+  m.nj = nj;
+  m.ns = ns;
   if (agg) {
-    char* h_mask = h_res + res_bytes + retry_bytes;
-    m.h_agg = (const uint8_t*)(h_mask + al256(ns1));
     m.out_job_sig96 = agg->sig96;
     m.out_job_count = agg->count;
-    m.d_joff = f.d_joff;
-    m.d_sig = d_sig;
-    m.nj = nj;
-    m.ns = ns;
-    uint8_t* d_mask = ws.take<uint8_t>(ns1);
-    m.d_mask = agg->mask ? d_mask : nullptr;
-    m.d_inc = ws.take<uint8_t>(ns1);
-    m.d_agg96 = ws.take<uint8_t>((size_t)nj * 96);
-    m.d_aggcnt = ws.take<uint32_t>(nj);
-    if (ws.off > ws.cap) {
-      ctx->err = "workspace overflow";
-      return LB_ERR_OUT_OF_MEMORY;
-    }
+    m.masked = agg->mask != nullptr;
     if (agg->mask && ns) {
-      memcpy(h_mask, agg->mask, ns);
-      LB_HIP(hipMemcpyAsync(d_mask, h_mask, ns, hipMemcpyHostToDevice, sl.st[0]));
+      memcpy(sm_h<uint8_t>(sl, L.h_mask), agg->mask, ns);
+      LB_HIP(hipMemcpyAsync(sm_d<uint8_t>(sl, L.d_mask), sm_h<uint8_t>(sl, L.h_mask), ns, hipMemcpyHostToDevice,
+                            sl.st[0]));
     }
   }
-  LB_TRY(run_pipeline(ctx, sl, nj, nj, d_areq, d_pk96, nullptr, nullptr, d_msgs, d_sig192, d_asig, d_seed, d_valid,
-                      d_err, nullptr, ws));
+  Slab ws{sl.d_ws, L.pipe1, sl.ws_cap};
+  LB_TRY(run_pipeline(ctx, sl, nj, nj, sm_d<const uint32_t>(sl, L.in[SI_AREQ]), sm_d<const uint8_t>(sl, L.d_pk96),
+                      nullptr, nullptr, sm_d<const uint8_t>(sl, L.in[SI_MSG]), sm_d<const uint8_t>(sl, L.d_sig192),
+                      sm_d<const uint32_t>(sl, L.in[SI_ASIG]), sm_d<const uint8_t>(sl, L.in[SI_SEED]), d_valid, d_err,
+                      nullptr, ws));
   if (agg) {
     // behind phase 1: the include decision on the device (the host's fast-path rule), then the
     // jobs' sums -- final when no job is retried, else redone behind phase 2 (sm_advance_launch)
     if (ns)
-      LB_STAGE("sm_job_sig", 0, k_sm_include, blocks_for(ns, 256), 256u, ns, nj, m.d_joff, (const uint8_t*)d_valid,
-               (const uint8_t*)d_err, (const uint8_t*)d_jbad, (const uint8_t*)d_jpkst, m.d_mask, m.d_inc);
+      LB_STAGE("sm_job_sig", 0, k_sm_include, blocks_for(ns, 256), 256u, ns, nj, sm_d<const uint32_t>(sl, L.in[SI_JOFF]),
+               (const uint8_t*)d_valid, (const uint8_t*)d_err, (const uint8_t*)d_jbad, (const uint8_t*)d_jpkst,
+               m.masked ? sm_d<const uint8_t>(sl, L.d_mask) : nullptr, sm_d<uint8_t>(sl, L.d_inc));
     LB_TRY(sm_job_sig(ctx, sl, m));
   }
-  LB_HIP(hipMemcpyAsync(h_res, d_valid, nj, hipMemcpyDeviceToHost, sl.st[0]));
-  LB_HIP(hipMemcpyAsync(h_res + al256(nj), d_err, nj, hipMemcpyDeviceToHost, sl.st[0]));
-  LB_HIP(hipMemcpyAsync(h_res + 2 * al256(nj), d_jbad, nj, hipMemcpyDeviceToHost, sl.st[0]));
-  LB_HIP(hipMemcpyAsync(h_res + 3 * al256(nj), d_jpkst, nj, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_HIP(hipMemcpyAsync(sm_h<uint8_t>(sl, L.h_valid), d_valid, nj, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_HIP(hipMemcpyAsync(sm_h<uint8_t>(sl, L.h_err), d_err, nj, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_HIP(hipMemcpyAsync(sm_h<uint8_t>(sl, L.h_jbad), d_jbad, nj, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_HIP(hipMemcpyAsync(sm_h<uint8_t>(sl, L.h_jpkst), d_jpkst, nj, hipMemcpyDeviceToHost, sl.st[0]));
   m.active = true;
   m.phase = 1;
-  m.by_index = by_index;
   m.mode = mode;
-  m.nj = nj;
-  m.ns = ns;
   m.out_valid = out_valid;
   m.out_job_fast = out_job_fast;
-  m.h_joff = h_joff;
-  m.h_res = (const uint8_t*)h_res;
-  m.h_rset = (uint32_t*)(h_res + res_bytes);
-  m.h_rout = (uint8_t*)(h_res + res_bytes + 2 * al256(4 * ns1));
-  m.d_pks = d_pks;
-  m.d_rows = d_rows;
-  m.d_sig = d_sig;
-  m.d_sst = d_sst;
-  m.d_msgs = d_msgs;
-  m.d_seed = d_seed;
-  m.ws_off = ws.off;
   return end_call_async(ctx, sl);
 }
 
@@ -3025,25 +2858,29 @@ int sm_advance_launch(lb_ctx* ctx, Slot& sl, bool block) {
   }
   LB_HIP(hipEventSynchronize(sl.done));
   const uint32_t nj = m.nj, ns = m.ns;
+  const SmLayout& L = m.lay;
+  uint32_t* h_rset = sm_h<uint32_t>(sl, L.h_rset);  // set indices, then (from ns) job indices
   if (m.phase == 2) {
-    for (uint32_t r = 0; r < m.nr; r++)
-      m.out_valid[m.h_rset[r]] = (m.h_rout[r] && m.h_rout[al256(ns) + r] == LB_REQ_OK) ? 1 : 0;
+    const uint8_t *rv = sm_h<const uint8_t>(sl, L.h_rvalid), *re = sm_h<const uint8_t>(sl, L.h_rerr);
+    for (uint32_t r = 0; r < m.nr; r++) m.out_valid[h_rset[r]] = (rv[r] && re[r] == LB_REQ_OK) ? 1 : 0;
   } else {
-    const uint8_t *v = m.h_res, *e = v + al256(nj), *jb = v + 2 * al256(nj), *pst = v + 3 * al256(nj);
+    const uint8_t *v = sm_h<const uint8_t>(sl, L.h_valid), *e = sm_h<const uint8_t>(sl, L.h_err),
+                  *jb = sm_h<const uint8_t>(sl, L.h_jbad), *pst = sm_h<const uint8_t>(sl, L.h_jpkst);
+    const uint32_t* h_joff = sm_h<const uint32_t>(sl, L.in[SI_JOFF]);
     uint32_t fast_sets = 0, retried_jobs = 0, nr = 0;
     for (uint32_t j = 0; j < nj; j++) {
       // fast path: aggregated set valid, every signature validated, pubkeys aggregated
       const bool fast = v[j] && e[j] == LB_REQ_OK && !jb[j] && pst[j] == LB_ST_OK;
       if (m.out_job_fast) m.out_job_fast[j] = fast ? 1 : 0;
-      const uint32_t a = m.h_joff[j], b = m.h_joff[j + 1];
+      const uint32_t a = h_joff[j], b = h_joff[j + 1];
       if (fast) {
         for (uint32_t i = a; i < b; i++) m.out_valid[i] = 1;
         fast_sets += b - a;
       } else if (b > a) {
         retried_jobs++;
         for (uint32_t i = a; i < b; i++) {
-          m.h_rset[nr] = i;
-          m.h_rset[(size_t)ns + nr] = j;
+          h_rset[nr] = i;
+          h_rset[(size_t)ns + nr] = j;
           nr++;
         }
       }
@@ -3052,30 +2889,33 @@ int sm_advance_launch(lb_ctx* ctx, Slot& sl, bool block) {
     m.retried_jobs = retried_jobs;
     m.fast_sets = fast_sets;
     if (nr) {
-      Bump ws{sl.d_ws, m.ws_off, sl.ws_cap};
-      uint32_t* d_rset = ws.take<uint32_t>(2 * (size_t)ns);
-      g2j* d_rsig = ws.take<g2j>(nr);
-      uint8_t* d_rst = ws.take<uint8_t>(nr);
-      uint8_t* d_rmsg = ws.take<uint8_t>((size_t)nr * 32);
-      uint32_t* d_ridx = ws.take<uint32_t>(nr);
-      uint32_t* d_rreq = ws.take<uint32_t>((size_t)nr + 1);
-      uint8_t* d_rvalid = ws.take<uint8_t>(nr);
-      uint8_t* d_rerr = ws.take<uint8_t>(nr);
-      if (ws.off > ws.cap) {
-        ctx->err = "workspace overflow";
-        return LB_ERR_OUT_OF_MEMORY;
-      }
-      LB_HIP(hipMemcpyAsync(d_rset, m.h_rset, sizeof(uint32_t) * 2 * (size_t)ns, hipMemcpyHostToDevice, sl.st[0]));
+      // phase 2's buffers for nr retries: inside the slab sized at submit (layout_same_message)
+      const SmLayout R = layout_same_message(m.shape, nr);
+      const bool by_index = m.shape.by_index;
+      uint32_t* d_rset = sm_d<uint32_t>(sl, R.d_rset);
+      g2j* d_rsig = sm_d<g2j>(sl, R.d_rsig);
+      uint8_t* d_rst = sm_d<uint8_t>(sl, R.d_rst);
+      uint8_t* d_rmsg = sm_d<uint8_t>(sl, R.d_rmsg);
+      uint32_t* d_ridx = sm_d<uint32_t>(sl, R.d_ridx);
+      uint32_t* d_rreq = sm_d<uint32_t>(sl, R.d_rreq);
+      uint8_t* d_rvalid = sm_d<uint8_t>(sl, R.d_rvalid);
+      uint8_t* d_rerr = sm_d<uint8_t>(sl, R.d_rerr);
+      const uint8_t* d_pks = sm_d<const uint8_t>(sl, L.in[SI_PK]);
+      const uint8_t* d_mask = m.masked ? sm_d<const uint8_t>(sl, L.d_mask) : nullptr;
+      Slab ws{sl.d_ws, R.pipe2, sl.ws_cap};
+      LB_HIP(hipMemcpyAsync(d_rset, h_rset, sizeof(uint32_t) * 2 * (size_t)ns, hipMemcpyHostToDevice, sl.st[0]));
       LB_ENQUEUE(sl.st[0], k_sm_retry_gather, blocks_for(nr), TPB, nr, (const uint32_t*)d_rset,
-                 (const uint32_t*)(d_rset + ns), m.d_sig, m.d_sst, m.d_msgs,
-                 m.by_index ? (const uint32_t*)m.d_pks : (const uint32_t*)nullptr, d_rsig, d_rst, d_rmsg, d_ridx, d_rreq);
-      LB_TRY(run_pipeline(ctx, sl, nr, nr, d_rreq, m.by_index ? m.d_rows : m.d_pks, nullptr, d_ridx, d_rmsg, nullptr,
-                          nullptr, m.d_seed, d_rvalid, d_rerr, nullptr, ws, false, d_rsig, d_rst));
-      LB_HIP(hipMemcpyAsync(m.h_rout, d_rvalid, nr, hipMemcpyDeviceToHost, sl.st[0]));
-      LB_HIP(hipMemcpyAsync(m.h_rout + al256(ns), d_rerr, nr, hipMemcpyDeviceToHost, sl.st[0]));
+                 (const uint32_t*)(d_rset + ns), sm_d<const g2j>(sl, L.d_sig), sm_d<const uint8_t>(sl, L.d_sst),
+                 sm_d<const uint8_t>(sl, L.in[SI_MSG]), by_index ? (const uint32_t*)d_pks : (const uint32_t*)nullptr,
+                 d_rsig, d_rst, d_rmsg, d_ridx, d_rreq);
+      LB_TRY(run_pipeline(ctx, sl, nr, nr, d_rreq, by_index ? sm_d<const uint8_t>(sl, L.in[SI_ROWS]) : d_pks, nullptr,
+                          d_ridx, d_rmsg, nullptr, nullptr, sm_d<const uint8_t>(sl, L.in[SI_SEED]), d_rvalid, d_rerr,
+                          nullptr, ws, false, d_rsig, d_rst));
+      LB_HIP(hipMemcpyAsync(sm_h<uint8_t>(sl, L.h_rvalid), d_rvalid, nr, hipMemcpyDeviceToHost, sl.st[0]));
+      LB_HIP(hipMemcpyAsync(sm_h<uint8_t>(sl, L.h_rerr), d_rerr, nr, hipMemcpyDeviceToHost, sl.st[0]));
       if (m.agg) {  // behind phase 2: the retried sets that verified alone join the sums
         LB_STAGE("sm_job_sig", 0, k_sm_include_retry, blocks_for(nr, 256), 256u, nr, (const uint32_t*)d_rset,
-                 (const uint8_t*)d_rvalid, (const uint8_t*)d_rerr, m.d_mask, m.d_inc);
+                 (const uint8_t*)d_rvalid, (const uint8_t*)d_rerr, d_mask, sm_d<uint8_t>(sl, L.d_inc));
         LB_TRY(sm_job_sig(ctx, sl, m));
       }
       LB_TRY(end_call(ctx, sl));
@@ -3088,8 +2928,8 @@ int sm_advance_launch(lb_ctx* ctx, Slot& sl, bool block) {
   sl.h_stats[0] = m.retried_jobs;
   sl.h_stats[1] = m.fast_sets;
   if (m.agg) {
-    memcpy(m.out_job_sig96, m.h_agg, (size_t)nj * 96);
-    memcpy(m.out_job_count, m.h_agg + al256((size_t)nj * 96), (size_t)nj * 4);
+    memcpy(m.out_job_sig96, sm_h<uint8_t>(sl, L.h_agg96), (size_t)nj * 96);
+    memcpy(m.out_job_count, sm_h<uint8_t>(sl, L.h_aggcnt), (size_t)nj * 4);
   }
   m.active = false;
   m.phase = 0;
@@ -3225,38 +3065,27 @@ int lb_aggregate_signature_groups(lb_ctx* ctx, uint32_t n_groups, const uint32_t
   if (sig_offsets[0] != 0) return LB_ERR_INVALID_ARGUMENT;
   for (uint32_t i = 0; i < n; i++)
     if (sig_offsets[i + 1] < sig_offsets[i]) return LB_ERR_INVALID_ARGUMENT;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  const size_t nb = sig_offsets[n];
-  LB_TRY(ensure_ws(ctx, nb + (size_t)n * (4 + sizeof(g2j) + 2) + (size_t)n_groups * (4 + 96 + 4) + 16 * 256));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void *d_s, *d_o, *d_g;
-  LB_TRY(upload(ctx, ws, signatures, nb, &d_s));
-  LB_TRY(upload(ctx, ws, sig_offsets, sizeof(uint32_t) * ((size_t)n + 1), &d_o));
-  LB_TRY(upload(ctx, ws, group_offsets, sizeof(uint32_t) * ((size_t)n_groups + 1), &d_g));
-  g2j* d_sig = ws.take<g2j>(n);
-  uint8_t* d_st = ws.take<uint8_t>(n);
-  uint8_t* d_inc = ws.take<uint8_t>(n);
-  uint8_t* d_out = ws.take<uint8_t>((size_t)n_groups * 96);
-  uint32_t* d_cnt = ws.take<uint32_t>(n_groups);
-  if (ws.off > ws.cap) {
-    ctx->err = "workspace overflow";
-    return LB_ERR_OUT_OF_MEMORY;
-  }
+  std::vector<uint8_t> st(n);
+  HelperCall c(ctx);
+  auto d_s = c.in(signatures, sig_offsets[n]);
+  auto d_o = c.in(sig_offsets, (size_t)n + 1);
+  auto d_g = c.in(group_offsets, (size_t)n_groups + 1);
+  auto d_sig = c.scratch<g2j>(n);
+  auto d_st = c.out(st.data(), n);
+  auto d_inc = c.scratch<uint8_t>(n);
+  auto d_out = c.out(out96, (size_t)n_groups * 96);
+  auto d_cnt = c.scratch<uint32_t>(n_groups);
+  LB_TRY(c.begin());
   if (flags & LB_AGG_NO_CHECK)
-    LB_LAUNCH(k_decode_sigs_nocheck, blocks_for(n), TPB, n, (const uint8_t*)d_s, (const uint32_t*)d_o, d_sig, d_st);
+    LB_LAUNCH(k_decode_sigs_nocheck, blocks_for(n), TPB, n, d_s, d_o, d_sig, d_st);
   else
-    LB_LAUNCH(k_decode_sigs, blocks_for(n), TPB, n, (const uint8_t*)d_s, (const uint32_t*)d_o, (const uint8_t*)nullptr,
-              d_sig, d_st);
+    LB_LAUNCH(k_decode_sigs, blocks_for(n), TPB, n, d_s, d_o, (const uint8_t*)nullptr, d_sig, d_st);
   LB_LAUNCH(k_inc_status, blocks_for(n, 256), 256u, n, (const uint8_t*)d_st, d_inc);
   const uint32_t jpw = job_sig_jobs_per_wg(n_groups, n);
   const uint32_t runs = (n_groups + jpw - 1) / jpw;
-  LB_LAUNCH(k_job_sig, runs < 16384u ? runs : 16384u, TPB, n_groups, jpw, (const uint32_t*)d_g, (const g2j*)d_sig,
-            (const uint8_t*)d_inc, d_out, d_cnt);
-  std::vector<uint8_t> st(n);
-  LB_HIP(hipMemcpyAsync(st.data(), d_st, n, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipMemcpyAsync(out96, d_out, (size_t)n_groups * 96, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
+  LB_LAUNCH(k_job_sig, runs < 16384u ? runs : 16384u, TPB, n_groups, jpw, d_g, (const g2j*)d_sig, (const uint8_t*)d_inc,
+            d_out, d_cnt);
+  LB_TRY(c.end());
   for (uint32_t g = 0; g < n_groups; g++) {
     out_bad_index[g] = -1;
     for (uint32_t i = group_offsets[g]; i < group_offsets[g + 1]; i++)
@@ -3314,21 +3143,19 @@ int lb_same_message_aggregates(lb_ctx* ctx, const lb_same_message_batch* b, uint
   LB_TRY(helper_slot(ctx));
   Slot& sl = ctx->slots[0];
   const uint32_t nj = b->n_jobs;
-  Bump ws{nullptr, 0, 0};
-  SmFront f;
-  LB_TRY(sm_front(ctx, sl, b, ctx->sm_mode, 0, 0, ws, f));
-  if (ws.off > ws.cap) {
-    ctx->err = "workspace overflow";
-    return LB_ERR_OUT_OF_MEMORY;
-  }
-  uint8_t* h_res = (uint8_t*)f.h + f.in_bytes;  // job_bad, pk status (al256(nj) each)
-  LB_HIP(hipMemcpyAsync(h_res, f.d_jbad, nj, hipMemcpyDeviceToHost, sl.st[0]));
-  LB_HIP(hipMemcpyAsync(h_res + al256(nj), f.d_jpkst, nj, hipMemcpyDeviceToHost, sl.st[0]));
-  LB_HIP(hipMemcpyAsync(out_pk96, f.d_pk96, (size_t)nj * 96, hipMemcpyDeviceToHost, sl.st[0]));
-  LB_HIP(hipMemcpyAsync(out_sig192, f.d_sig192, (size_t)nj * 192, hipMemcpyDeviceToHost, sl.st[0]));
+  SmShape shape;
+  SmLayout L;
+  LB_TRY(sm_prepare(ctx, sl, b, false, true, shape, L));
+  LB_TRY(sm_front(ctx, sl, b, ctx->sm_mode, shape, L));
+  const uint8_t *h_jbad = sm_h<const uint8_t>(sl, L.h_jbad), *h_jpkst = sm_h<const uint8_t>(sl, L.h_jpkst);
+  LB_HIP(hipMemcpyAsync(sm_h<uint8_t>(sl, L.h_jbad), sm_d<uint8_t>(sl, L.d_jbad), nj, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_HIP(hipMemcpyAsync(sm_h<uint8_t>(sl, L.h_jpkst), sm_d<uint8_t>(sl, L.d_jpkst), nj, hipMemcpyDeviceToHost,
+                        sl.st[0]));
+  LB_HIP(hipMemcpyAsync(out_pk96, sm_d<uint8_t>(sl, L.d_pk96), (size_t)nj * 96, hipMemcpyDeviceToHost, sl.st[0]));
+  LB_HIP(hipMemcpyAsync(out_sig192, sm_d<uint8_t>(sl, L.d_sig192), (size_t)nj * 192, hipMemcpyDeviceToHost, sl.st[0]));
   LB_HIP(hipStreamSynchronize(sl.st[0]));
   for (uint32_t j = 0; j < nj; j++) {
-    const bool bad = h_res[j] || h_res[al256(nj) + j] != LB_ST_OK;
+    const bool bad = h_jbad[j] || h_jpkst[j] != LB_ST_OK;
     out_job_bad[j] = bad ? 1 : 0;
     if (bad) {
       memset(out_pk96 + (size_t)j * 96, 0, 96);
@@ -3341,68 +3168,44 @@ int lb_same_message_aggregates(lb_ctx* ctx, const lb_same_message_batch* b, uint
 int lb_pairing(lb_ctx* ctx, uint32_t n, const uint8_t* g1_96, const uint8_t* g2_192, uint8_t* out576) {
   if (!ctx || (n && (!g1_96 || !g2_192 || !out576))) return LB_ERR_INVALID_ARGUMENT;
   if (n == 0) return LB_OK;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  LB_TRY(ensure_ws(ctx, (size_t)n * (96 + 192 + 576) + 8192));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void *d1, *d2;
-  LB_TRY(upload(ctx, ws, g1_96, (size_t)n * 96, &d1));
-  LB_TRY(upload(ctx, ws, g2_192, (size_t)n * 192, &d2));
-  uint8_t* d_out = ws.take<uint8_t>((size_t)n * 576);
-  LB_LAUNCH(k_pairing, blocks_for(n), TPB, n, (const uint8_t*)d1, (const uint8_t*)d2, d_out);
-  LB_HIP(hipMemcpyAsync(out576, d_out, (size_t)n * 576, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  return LB_OK;
+  HelperCall c(ctx);
+  auto d1 = c.in(g1_96, (size_t)n * 96);
+  auto d2 = c.in(g2_192, (size_t)n * 192);
+  auto d_out = c.out(out576, (size_t)n * 576);
+  LB_TRY(c.begin());
+  LB_LAUNCH(k_pairing, blocks_for(n), TPB, n, d1, d2, d_out);
+  return c.end();
 }
 
 int lb_batch_scalars(lb_ctx* ctx, const uint8_t* seed, uint32_t first, uint32_t n, uint64_t* out) {
   if (!ctx || !seed || (n && !out)) return LB_ERR_INVALID_ARGUMENT;
   if (n == 0) return LB_OK;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  LB_TRY(ensure_ws(ctx, (size_t)n * 8 + 8192));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void* d_seed;
-  LB_TRY(upload(ctx, ws, seed, 32, &d_seed));
-  uint64_t* d_out = ws.take<uint64_t>(n);
-  LB_LAUNCH(k_scalars, blocks_for(n), TPB, (const uint8_t*)d_seed, first, n, d_out);
-  LB_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  return LB_OK;
+  HelperCall c(ctx);
+  auto d_seed = c.in(seed, 32);
+  auto d_out = c.out(out, n);
+  LB_TRY(c.begin());
+  LB_LAUNCH(k_scalars, blocks_for(n), TPB, d_seed, first, n, d_out);
+  return c.end();
 }
 
+// [k_i] P_i for n points of `bytes` uncompressed bytes each (kernel: k_g1_mul / k_g2_mul)
+static int point_mul(lb_ctx* ctx, uint32_t n, size_t bytes, const uint8_t* in, const uint64_t* k, uint8_t* out,
+                     void (*kernel)(uint32_t, const uint8_t*, const uint64_t*, uint8_t*)) {
+  if (!ctx || (n && (!in || !k || !out))) return LB_ERR_INVALID_ARGUMENT;
+  if (n == 0) return LB_OK;
+  HelperCall c(ctx);
+  auto d_in = c.in(in, (size_t)n * bytes);
+  auto d_k = c.in(k, n);
+  auto d_out = c.out(out, (size_t)n * bytes);
+  LB_TRY(c.begin());
+  LB_LAUNCH(kernel, blocks_for(n), TPB, n, (const uint8_t*)d_in, (const uint64_t*)d_k, (uint8_t*)d_out);
+  return c.end();
+}
 int lb_g1_mul(lb_ctx* ctx, uint32_t n, const uint8_t* in96, const uint64_t* k, uint8_t* out96) {
-  if (!ctx || (n && (!in96 || !k || !out96))) return LB_ERR_INVALID_ARGUMENT;
-  if (n == 0) return LB_OK;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  LB_TRY(ensure_ws(ctx, (size_t)n * (96 * 2 + 8) + 8192));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void *d_in, *d_k;
-  LB_TRY(upload(ctx, ws, in96, (size_t)n * 96, &d_in));
-  LB_TRY(upload(ctx, ws, k, (size_t)n * 8, &d_k));
-  uint8_t* d_out = ws.take<uint8_t>((size_t)n * 96);
-  LB_LAUNCH(k_g1_mul, blocks_for(n), TPB, n, (const uint8_t*)d_in, (const uint64_t*)d_k, d_out);
-  LB_HIP(hipMemcpyAsync(out96, d_out, (size_t)n * 96, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  return LB_OK;
+  return point_mul(ctx, n, 96, in96, k, out96, k_g1_mul);
 }
-
 int lb_g2_mul(lb_ctx* ctx, uint32_t n, const uint8_t* in192, const uint64_t* k, uint8_t* out192) {
-  if (!ctx || (n && (!in192 || !k || !out192))) return LB_ERR_INVALID_ARGUMENT;
-  if (n == 0) return LB_OK;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  LB_TRY(ensure_ws(ctx, (size_t)n * (192 * 2 + 8) + 8192));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void *d_in, *d_k;
-  LB_TRY(upload(ctx, ws, in192, (size_t)n * 192, &d_in));
-  LB_TRY(upload(ctx, ws, k, (size_t)n * 8, &d_k));
-  uint8_t* d_out = ws.take<uint8_t>((size_t)n * 192);
-  LB_LAUNCH(k_g2_mul, blocks_for(n), TPB, n, (const uint8_t*)d_in, (const uint64_t*)d_k, d_out);
-  LB_HIP(hipMemcpyAsync(out192, d_out, (size_t)n * 192, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  return LB_OK;
+  return point_mul(ctx, n, 192, in192, k, out192, k_g2_mul);
 }
 
 // sum_i (a_i + b_i lambda) P_i through the merged check's bucket MSM (k_msm.hip),
@@ -3413,38 +3216,27 @@ int lb_g2_msm(lb_ctx* ctx, uint32_t n, const uint8_t* in192, const uint64_t* raw
     ctx->err = "lb_g2_msm: too many points";
     return LB_ERR_INVALID_ARGUMENT;
   }
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
   const uint32_t ns = n ? n : 1;
   const size_t n_ent = 2 * (size_t)ns * LB_MSM_W, max_chunks = n_ent / LB_MSM_T + LB_MSM_BUCKETS;
-  LB_TRY(ensure_ws(ctx, (size_t)ns * (192 + 8 + sizeof(g2j) + 1) + 2 * n_ent * 4 + max_chunks * sizeof(g2j) +
-                            (LB_MSM_BUCKETS + LB_MSM_POS) * sizeof(g2j) + 4 * (LB_MSM_BUCKETS + 1) * 4 + 64 * 256));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void *d_in = nullptr, *d_raw = nullptr;
-  if (n) {
-    LB_TRY(upload(ctx, ws, in192, (size_t)n * 192, &d_in));
-    LB_TRY(upload(ctx, ws, raw, (size_t)n * 8, &d_raw));
-  }
-  g2j* d_pts = ws.take<g2j>(ns);
-  uint8_t* d_st = ws.take<uint8_t>(ns);
-  uint32_t* d_req = ws.take<uint32_t>(2);
-  uint32_t* d_keys = ws.take<uint32_t>(n_ent);
-  uint32_t* d_sorted = ws.take<uint32_t>(n_ent);
-  uint32_t* d_hist = ws.take<uint32_t>(4 * (LB_MSM_BUCKETS + 1));
-  g2j* d_csum = ws.take<g2j>(max_chunks);
-  g2j* d_bsum = ws.take<g2j>(LB_MSM_BUCKETS);
-  g2j* d_G = ws.take<g2j>(LB_MSM_POS);
-  g2a* d_S = ws.take<g2a>(1);
-  uint8_t* d_out = ws.take<uint8_t>(192);
-  if (ws.off > ws.cap) {
-    ctx->err = "workspace overflow";
-    return LB_ERR_OUT_OF_MEMORY;
-  }
+  const uint32_t req[2] = {0, n};
+  HelperCall c(ctx);
+  auto d_in = c.in(in192, (size_t)n * 192, n != 0);
+  auto d_raw = c.in(raw, n, n != 0);
+  auto d_req = c.in(req, 2);
+  auto d_pts = c.scratch<g2j>(ns);
+  auto d_st = c.scratch<uint8_t>(ns);
+  auto d_keys = c.scratch<uint32_t>(n_ent);
+  auto d_sorted = c.scratch<uint32_t>(n_ent);
+  auto d_hist = c.scratch<uint32_t>(4 * (LB_MSM_BUCKETS + 1));
+  auto d_csum = c.scratch<g2j>(max_chunks);
+  auto d_bsum = c.scratch<g2j>(LB_MSM_BUCKETS);
+  auto d_G = c.scratch<g2j>(LB_MSM_POS);
+  auto d_S = c.scratch<g2a>(1);
+  auto d_out = c.out(out192, 192);
+  LB_TRY(c.begin());
   uint32_t* d_off = d_hist + (LB_MSM_BUCKETS + 1);
   uint32_t* d_coff = d_off + (LB_MSM_BUCKETS + 1);
   uint32_t* d_cur = d_coff + (LB_MSM_BUCKETS + 1);
-  const uint32_t req[2] = {0, n};
-  LB_HIP(hipMemcpyAsync(d_req, req, sizeof(req), hipMemcpyHostToDevice, ctx->stream));
   LB_HIP(hipMemsetAsync(d_hist, 0, (LB_MSM_BUCKETS + 1) * sizeof(uint32_t), ctx->stream));
   if (n) {
     LB_LAUNCH(k_msm_load, blocks_for(n), TPB, n, (const uint8_t*)d_in, d_pts, d_st);
@@ -3461,10 +3253,16 @@ int lb_g2_msm(lb_ctx* ctx, uint32_t n, const uint8_t* in192, const uint64_t* raw
   LB_LAUNCH(k_msm_bits<LB_MSM_BITS_TPB>, LB_MSM_POS, LB_MSM_BITS_TPB, (const g2j*)d_bsum, d_G);
   LB_LAUNCH(k_msm_final, 1u, TPB, (const g2j*)d_G, d_S);
   LB_LAUNCH(k_g2a_serialize, 1u, TPB, 1u, (const g2a*)d_S, d_out);
-  LB_HIP(hipMemcpyAsync(out192, d_out, 192, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  return LB_OK;
+  return c.end();
 }
+
+// A timing event that lives as long as its scope
+struct ScopedEvent {
+  hipEvent_t e = nullptr;
+  ~ScopedEvent() {
+    if (e) (void)hipEventDestroy(e);
+  }
+};
 
 // Round program on n instances, one workgroup each (tests, timing): prog_words
 // == nullptr runs the embedded program `prog` (LB_LP_PROG_*), else the caller's
@@ -3472,43 +3270,6 @@ int lb_g2_msm(lb_ctx* ctx, uint32_t n, const uint8_t* in192, const uint64_t* raw
 // of 16 words (canonical Montgomery limbs), in_flags: n x n_inflag words; out16:
 // n x n_out records, out_flags: n x n_outflag words; *out_ms: kernel time;
 // stamps (optional): s_memtime after each round of instance 0.
-static int lp_program_run(lb_ctx* ctx, const uint32_t* d_prog, uint32_t n, uint32_t n_in, uint32_t n_inflag,
-                          uint32_t n_out, uint32_t n_outflag, uint32_t n_rounds, const uint32_t* in16,
-                          const uint32_t* in_flags, uint32_t* out16, uint32_t* out_flags, float* out_ms,
-                          uint64_t* stamps, Bump& ws) {
-  const size_t in_w = (size_t)n * n_in * 16, fl_w = (size_t)n * n_inflag + 1, out_w = (size_t)n * n_out * 16,
-               ofl_w = (size_t)n * n_outflag + 1;
-  void* d_in = nullptr;
-  LB_TRY(upload(ctx, ws, in16, in_w * 4, &d_in));
-  uint32_t* d_fl = ws.take<uint32_t>(fl_w);
-  if (n_inflag) LB_HIP(hipMemcpyAsync(d_fl, in_flags, (fl_w - 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  uint32_t* d_out = ws.take<uint32_t>(out_w);
-  uint32_t* d_ofl = ws.take<uint32_t>(ofl_w);
-  unsigned long long* d_st = stamps ? ws.take<unsigned long long>((size_t)(n_rounds + 1) * LB_LP_STAMPS) : nullptr;
-  if (ws.off > ws.cap) {
-    ctx->err = "workspace overflow";
-    return LB_ERR_OUT_OF_MEMORY;
-  }
-  hipEvent_t e0, e1;
-  LB_HIP(hipEventCreate(&e0));
-  LB_HIP(hipEventCreate(&e1));
-  LB_HIP(hipEventRecord(e0, ctx->stream));
-  LB_LAUNCH(k_lp_program, n, LB_LP_TPB, d_prog, n, (const uint32_t*)d_in, n_in * 16u, (const uint32_t*)d_fl, n_inflag,
-            d_out, n_out * 16u, d_ofl, n_outflag, d_st);
-  LB_HIP(hipEventRecord(e1, ctx->stream));
-  LB_HIP(hipMemcpyAsync(out16, d_out, out_w * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (n_outflag) LB_HIP(hipMemcpyAsync(out_flags, d_ofl, (ofl_w - 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (stamps)
-    LB_HIP(hipMemcpyAsync(stamps, d_st, (size_t)n_rounds * LB_LP_STAMPS * 8, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (out_ms) *out_ms = ms;
-  return LB_OK;
-}
-
 int lb_lp_program_run(lb_ctx* ctx, uint32_t prog, const uint32_t* prog_words, size_t n_words, uint32_t n,
                       const uint32_t* in16, const uint32_t* in_flags, uint32_t* out16, uint32_t* out_flags,
                       float* out_ms, uint64_t* stamps) {
@@ -3520,26 +3281,38 @@ int lb_lp_program_run(lb_ctx* ctx, uint32_t prog, const uint32_t* prog_words, si
       (prog == LB_LP_PROG_MTAIL_CHECK_WIDE || prog == LB_LP_PROG_MTAIL_PARTIAL_WIDE))
     return LB_ERR_INVALID_ARGUMENT;
   if (prog_words && (n_words < LB_LP_HDR || prog_words[0] != 0x4C500004u)) return LB_ERR_INVALID_ARGUMENT;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
   const uint32_t* hw = prog_words ? prog_words : lb_lp_blob + LB_LP_PROGS[prog].off;
   const uint32_t n_rounds = hw[1], n_in = hw[5], n_inflag = hw[6], n_out = hw[7], n_outflag = hw[8];
   if ((n_inflag && !in_flags) || (n_outflag && !out_flags)) return LB_ERR_INVALID_ARGUMENT;
-  const size_t io = 4 * ((size_t)n * (n_in + n_out) * 16 + (size_t)n * (n_inflag + n_outflag) + 2) +
-                    8 * (size_t)(n_rounds + 1) * LB_LP_STAMPS;
-  LB_TRY(ensure_ws(ctx, io + (prog_words ? 4 * n_words : 0) + 16384));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  const uint32_t* d_prog;
-  if (prog_words) {
-    void* d = nullptr;
-    LB_TRY(upload(ctx, ws, prog_words, n_words * 4, &d));
-    d_prog = (const uint32_t*)d;
-  } else {
-    LB_TRY(lp_ensure(ctx));
-    d_prog = ctx->d_lp + LB_LP_PROGS[prog].off;
-  }
-  return lp_program_run(ctx, d_prog, n, n_in, n_inflag, n_out, n_outflag, n_rounds, in16, in_flags, out16, out_flags,
-                        out_ms, stamps, ws);
+  // (the flag buffers hold one word more than the host's arrays, the stamps one round more)
+  const size_t fl_w = (size_t)n * n_inflag + 1, out_w = (size_t)n * n_out * 16, ofl_w = (size_t)n * n_outflag + 1;
+  HelperCall c(ctx);
+  auto d_words = c.in(prog_words, n_words, prog_words != nullptr);
+  auto d_in = c.in(in16, (size_t)n * n_in * 16);
+  auto d_fl = c.scratch<uint32_t>(fl_w);
+  auto d_out = c.scratch<uint32_t>(out_w);
+  auto d_ofl = c.scratch<uint32_t>(ofl_w);
+  auto d_st = c.scratch<unsigned long long>((size_t)(n_rounds + 1) * LB_LP_STAMPS, stamps != nullptr);
+  LB_TRY(c.begin());
+  if (!prog_words) LB_TRY(lp_ensure(ctx));
+  const uint32_t* d_prog = prog_words ? (const uint32_t*)d_words : ctx->d_lp + LB_LP_PROGS[prog].off;
+  if (n_inflag) LB_HIP(hipMemcpyAsync(d_fl, in_flags, (fl_w - 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+  ScopedEvent e0, e1;
+  LB_HIP(hipEventCreate(&e0.e));
+  LB_HIP(hipEventCreate(&e1.e));
+  LB_HIP(hipEventRecord(e0.e, ctx->stream));
+  LB_LAUNCH(k_lp_program, n, LB_LP_TPB, d_prog, n, d_in, n_in * 16u, (const uint32_t*)d_fl, n_inflag, d_out,
+            n_out * 16u, d_ofl, n_outflag, d_st);
+  LB_HIP(hipEventRecord(e1.e, ctx->stream));
+  LB_HIP(hipMemcpyAsync(out16, d_out, out_w * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (n_outflag) LB_HIP(hipMemcpyAsync(out_flags, d_ofl, (ofl_w - 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (stamps)
+    LB_HIP(hipMemcpyAsync(stamps, d_st, (size_t)n_rounds * LB_LP_STAMPS * 8, hipMemcpyDeviceToHost, ctx->stream));
+  LB_TRY(c.end());
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, e0.e, e1.e);
+  if (out_ms) *out_ms = ms;
+  return LB_OK;
 }
 
 int lb_set_latency_path(lb_ctx* ctx, uint32_t max_sets) {
@@ -3554,34 +3327,24 @@ int lb_set_latency_path(lb_ctx* ctx, uint32_t max_sets) {
 int lb_sk_to_pk(lb_ctx* ctx, uint32_t n, const uint8_t* sk32, uint8_t* out96) {
   if (!ctx || (n && (!sk32 || !out96))) return LB_ERR_INVALID_ARGUMENT;
   if (n == 0) return LB_OK;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  LB_TRY(ensure_ws(ctx, (size_t)n * (32 + 96) + 8192));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void* d_k;
-  LB_TRY(upload(ctx, ws, sk32, (size_t)n * 32, &d_k));
-  uint8_t* d_out = ws.take<uint8_t>((size_t)n * 96);
-  LB_LAUNCH(k_sk_to_pk, blocks_for(n), TPB, n, (const uint8_t*)d_k, d_out);
-  LB_HIP(hipMemcpyAsync(out96, d_out, (size_t)n * 96, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  return LB_OK;
+  HelperCall c(ctx);
+  auto d_k = c.in(sk32, (size_t)n * 32);
+  auto d_out = c.out(out96, (size_t)n * 96);
+  LB_TRY(c.begin());
+  LB_LAUNCH(k_sk_to_pk, blocks_for(n), TPB, n, d_k, d_out);
+  return c.end();
 }
 
 int lb_sign(lb_ctx* ctx, uint32_t n, const uint8_t* sk32, const uint8_t* messages, uint8_t* out96) {
   if (!ctx || (n && (!sk32 || !messages || !out96))) return LB_ERR_INVALID_ARGUMENT;
   if (n == 0) return LB_OK;
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  LB_TRY(ensure_ws(ctx, (size_t)n * (32 + 32 + 96) + 8192));
-  Bump ws{ctx->slots[0].d_ws, 0, ctx->slots[0].ws_cap};
-  void *d_k, *d_m;
-  LB_TRY(upload(ctx, ws, sk32, (size_t)n * 32, &d_k));
-  LB_TRY(upload(ctx, ws, messages, (size_t)n * 32, &d_m));
-  uint8_t* d_out = ws.take<uint8_t>((size_t)n * 96);
-  LB_LAUNCH(k_sign, blocks_for(n), TPB, n, (const uint8_t*)d_k, (const uint8_t*)d_m, d_out);
-  LB_HIP(hipMemcpyAsync(out96, d_out, (size_t)n * 96, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  return LB_OK;
+  HelperCall c(ctx);
+  auto d_k = c.in(sk32, (size_t)n * 32);
+  auto d_m = c.in(messages, (size_t)n * 32);
+  auto d_out = c.out(out96, (size_t)n * 96);
+  LB_TRY(c.begin());
+  LB_LAUNCH(k_sign, blocks_for(n), TPB, n, d_k, d_m, d_out);
+  return c.end();
 }
 
 }  // extern "C"
@@ -3603,17 +3366,38 @@ int kzg_ensure(lb_ctx* ctx, KzgBufs& b) {
   LB_HIP(hipSetDevice(ctx->device));
   LB_TRY(helper_slot(ctx));
   KzgState& k = ctx->kzg;
+  // the buffers of a call of LB_KZG_MAX_BLOBS blobs: the workspace is this list's total
   constexpr size_t M = LB_KZG_MAX_BLOBS;
-  constexpr size_t kBytes = M * (LB_KZG_BLOB_BYTES + 48 + 48 + 32 + 32 + 1 + 2 + 1 + 3 * 32) + 2 * 32 + 16 +
-                            sizeof(g1j) * (2 * M + 1 + 3 * M + 1 + 2 * M) + sizeof(fp12) * 2 * M + 32 * 256;
+  Carve<14> c;
+  auto blobs = c.scratch<uint8_t>(M * LB_KZG_BLOB_BYTES);
+  auto com = c.scratch<uint8_t>(M * 48);
+  auto proofs = c.scratch<uint8_t>(M * 48);
+  auto z = c.scratch<uint8_t>(M * 32);
+  auto y = c.scratch<uint8_t>(M * 32);
+  auto status = c.scratch<uint8_t>(M);
+  auto pt_status = c.scratch<uint8_t>(2 * M);
+  auto skip = c.scratch<uint8_t>(16);
+  auto scalars = c.scratch<uint8_t>((3 * M + 1) * 32);
+  auto verdict = c.scratch<uint8_t>(M);
+  auto P = c.scratch<g1j>(2 * M + 1);
+  auto lad = c.scratch<g1j>(3 * M + 1);
+  auto AB = c.scratch<g1j>(2 * M);
+  auto f = c.scratch<fp12>(2 * M);
+  const size_t bytes = c.layout();
   if (!k.d_ws) {
-    if (hipMalloc(&k.d_ws, kBytes) != hipSuccess) {
+    if (hipMalloc(&k.d_ws, bytes) != hipSuccess) {
       k.d_ws = nullptr;
       ctx->err = "hipMalloc KZG workspace failed";
       return LB_ERR_OUT_OF_MEMORY;
     }
-    k.ws_cap = kBytes;
+    k.ws_cap = bytes;
   }
+  if (!c.fits(k.ws_cap)) {
+    ctx->err = "KZG workspace overflow";
+    return LB_ERR_OUT_OF_MEMORY;
+  }
+  c.bind(k.d_ws);
+  b = KzgBufs{blobs, com, proofs, z, y, status, pt_status, skip, scalars, verdict, P, lad, AB, f};
   if (!k.d_neg_tau && hipMalloc(&k.d_neg_tau, 2 * sizeof(g2a)) != hipSuccess) {
     k.d_neg_tau = nullptr;
     ctx->err = "hipMalloc KZG setup failed";
@@ -3634,25 +3418,6 @@ int kzg_ensure(lb_ctx* ctx, KzgBufs& b) {
       return LB_ERR_DEVICE;
     }
     k.d_roots = d;
-  }
-  Bump ws{k.d_ws, 0, k.ws_cap};
-  b.blobs = ws.take<uint8_t>(M * LB_KZG_BLOB_BYTES);
-  b.com = ws.take<uint8_t>(M * 48);
-  b.proofs = ws.take<uint8_t>(M * 48);
-  b.z = ws.take<uint8_t>(M * 32);
-  b.y = ws.take<uint8_t>(M * 32);
-  b.status = ws.take<uint8_t>(M);
-  b.pt_status = ws.take<uint8_t>(2 * M);
-  b.skip = ws.take<uint8_t>(16);
-  b.scalars = ws.take<uint8_t>((3 * M + 1) * 32);
-  b.verdict = ws.take<uint8_t>(M);
-  b.P = ws.take<g1j>(2 * M + 1);
-  b.lad = ws.take<g1j>(3 * M + 1);
-  b.AB = ws.take<g1j>(2 * M);
-  b.f = ws.take<fp12>(2 * M);
-  if (ws.off > ws.cap) {
-    ctx->err = "KZG workspace overflow";
-    return LB_ERR_OUT_OF_MEMORY;
   }
   return LB_OK;
 }

@@ -8,6 +8,8 @@
 //   plan_upper       the plan whose layout bounds that of any call with at most that many
 //                    requests and sets (pipeline_ws_bytes: sizing ahead of a call)
 //   layout_pipeline  every workspace buffer of a plan: offsets and the total, in bytes
+//                    (carved by bls_carve.h's rule, which also lays out what the callers put
+//                    in front of the pipeline's workspace)
 //
 // run_pipeline builds plan and layout, checks the slab once, and enqueues; nothing below the
 // plan reads a switch or compares a size.
@@ -17,6 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "bls_carve.h"
 #include "bls_limits.h"
 
 namespace lb {
@@ -418,9 +421,6 @@ inline PipePlan plan_upper(const PipeConfig& c, uint32_t n_req, uint32_t n_sets)
 }
 
 // ---- the layout -------------------------------------------------------------------------
-// Record sizes of the device types (bls_host.hip pins them to sizeof with static_assert)
-static constexpr size_t SZ_G2J = 288, SZ_G1J = 144, SZ_G2A = 196 /* x, y and the infinity flag */, SZ_FP12 = 576;
-
 // One entry per workspace buffer of run_pipeline, in the order they are laid out
 enum PipeBuf : int {
   PB_SIG, PB_RSIG, PB_Q, PB_H, PB_PK, PB_RPK, PB_F_SETS, PB_LINES, PB_SINGLE, PB_PK_ST, PB_SIG_ST,
@@ -442,43 +442,26 @@ static constexpr const char* kPipeBufNames[PB_COUNT] = {
     "Fx", "off2", "acc_F", "acc_bad", "acc_err", "partial"};
 
 struct PipeLayout {
-  static constexpr size_t kAbsent = ~(size_t)0;
+  static constexpr size_t kAbsent = kCarveAbsent;
   size_t off[PB_COUNT];    // offset from the slab's base, 256-aligned (kAbsent: the plan has no such buffer)
   size_t size[PB_COUNT];   // bytes
   size_t bytes = 0;        // end of the last buffer - start
   bool has(PipeBuf b) const { return off[b] != kAbsent; }
 };
 
-// The latency path's workspace (run_lp's buffers, for a plan with latency_path): what a slab sized
-// by pipeline_ws_bytes must also hold, since a small call takes either path.
-inline size_t lp_ws_bytes(size_t ns) {
-  const size_t sizes[] = {SZ_G1J * ns, ns, 4 * ns * LB_LP_NIN * 16, 4 * ns * LB_LP_NFL, ns, 4 * ns,
-                          4 * ns * 12 * 16, 4 * (size_t)LB_LP_TREE_LEVELS * ns, 8 * 4};
-  size_t off = 0;
-  for (size_t z : sizes) off = ((off + 255) & ~(size_t)255) + z;
-  return off;
-}
-
-// Every buffer of a plan, laid out from `start` (the slab's fill when the call arrives) the way
-// Bump::take does: each aligned to 256 B, in one fixed order, so a plan that asks for more or
+// Every buffer of a plan, laid out from `start` (the slab's fill when the call arrives) by
+// carve_take: each aligned to 256 B, in one fixed order, so a plan that asks for more or
 // larger buffers never ends before one that asks for fewer or smaller.
 inline PipeLayout layout_pipeline(const PipePlan& p, size_t start = 0) {
   PipeLayout L;
   size_t at = start;
   const auto take = [&](PipeBuf b, bool present, size_t count, size_t elem) {
-    if (!present) {
-      L.off[b] = PipeLayout::kAbsent;
-      L.size[b] = 0;
-      return;
-    }
-    at = (at + 255) & ~(size_t)255;
-    L.off[b] = at;
-    L.size[b] = count * elem;
-    at += count * elem;
+    L.off[b] = carve_take(at, count * elem, present);
+    L.size[b] = present ? count * elem : 0;
   };
-  if (p.latency_path) {
+  if (p.latency_path) {  // run_lp's list (layout_lp) is the whole of it
     for (int b = 0; b < PB_COUNT; b++) take((PipeBuf)b, false, 0, 0);
-    L.bytes = ((start + 255) & ~(size_t)255) - start + lp_ws_bytes(p.ns);
+    L.bytes = layout_lp(p.ns, true, start).end - start;
     return L;
   }
   const size_t ns = p.ns, nr = p.n_req, nr1 = p.nr1;
