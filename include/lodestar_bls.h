@@ -520,8 +520,9 @@ int lb_signing_roots_chunks(lb_ctx* ctx, uint32_t n, uint32_t m, const uint8_t* 
  * Scheduling: synchronous calls on buffers and a stream state of their own.  Like
  * lb_aggregate_signature_groups they wait for the context's calls in flight (which retire
  * normally: their tickets stay valid for lb_wait / lb_poll); they take no slot, issue no
- * ticket and never touch the pubkey table.  blobToKzgCommitment / computeBlobKzgProof are
- * not provided (they need the Lagrange G1 setup and an MSM over it). */
+ * ticket and never touch the pubkey table.  blobToKzgCommitment / computeBlobKzgProof /
+ * computeKzgProof are the lb_kzg_blob_commitments / lb_kzg_blob_proofs / lb_kzg_compute_proofs
+ * calls further down; they need the Lagrange G1 setup (lb_kzg_load_setup_g1), not [tau]_2. */
 #define LB_KZG_BLOB_BYTES 131072
 #define LB_KZG_MAX_BLOBS 64
 #define LB_KZG_OK 0
@@ -556,6 +557,39 @@ int lb_kzg_blob_challenges(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const 
                            uint8_t* out_z32, uint8_t* out_y32, uint8_t* out_status);
 int lb_kzg_evaluate(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* z32, uint8_t* out_y32,
                     uint8_t* out_status);
+
+/* ---- blob KZG commitments and proofs (deneb) ---------------------------------
+ * ckzg.blobToKzgCommitment / computeBlobKzgProof (BN/util/kzg.ts:15-22): a fixed-base MSM of
+ * 4096 scalars over KZG_SETUP_G1_LAGRANGE, for a proof after the quotient polynomial in Fr.
+ * The two setups are independent: verification needs lb_kzg_load_setup, these calls need
+ * lb_kzg_load_setup_g1 (without it: LB_ERR_INVALID_ARGUMENT, "no G1 setup loaded").
+ * Statuses as above; an item with a status gets all-zero outputs and the call's other items
+ * are still computed.  n == 0 -> LB_OK, nothing launched; n > LB_KZG_MAX_BLOBS or a NULL
+ * pointer -> LB_ERR_INVALID_ARGUMENT, nothing written.  Scheduling as for verification.
+ *
+ * Load the 4096 compressed G1 Lagrange points of trusted_setup.txt, in FILE order (the spec's
+ * KZG_SETUP_G1_LAGRANGE is its bit-reversal permutation, applied here), and build the window
+ * table [2^(8j)] L[i], j < 32, on the device.  Every point is checked as validate_kzg_g1
+ * does (the infinity encoding is accepted).  A bad point -> LB_ERR_INVALID_ARGUMENT,
+ * *out_bad_index (optional) = the first one's index in file order (else -1), lb_last_error
+ * says which check failed, and the previously loaded table stays in use. */
+int lb_kzg_load_setup_g1(lb_ctx* ctx, const uint8_t* g1_lagrange48, int32_t* out_bad_index);
+/* 1 when a G1 setup is loaded, 0 when not (NULL context: LB_ERR_INVALID_ARGUMENT);
+ * lb_kzg_setup_loaded speaks of the G2 side only. */
+int lb_kzg_setup_g1_loaded(const lb_ctx* ctx);
+/* blob_to_kzg_commitment of n blobs.  LB_KZG_BAD_BLOB: a field element >= r. */
+int lb_kzg_blob_commitments(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, uint8_t* out_commitments48,
+                            uint8_t* out_status);
+/* compute_blob_kzg_proof of n (blob, commitment) pairs.  The commitment is decoded
+ * (LB_KZG_BAD_COMMITMENT) but not compared with the blob; its 48 bytes are hashed as given. */
+int lb_kzg_blob_proofs(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* commitments48,
+                       uint8_t* out_proofs48, uint8_t* out_status);
+/* compute_kzg_proof(blob, z) -> (proof, y = blob(z)).  LB_KZG_BAD_SCALAR: z >= r. */
+int lb_kzg_compute_proofs(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* z32, uint8_t* out_proofs48,
+                          uint8_t* out_y32, uint8_t* out_status);
+/* Stage-level, for tests: out48[k] = sum_i scalars32[k][i] L[i] over the loaded setup in spec
+ * order (n_jobs x 4096 x 32 bytes, big-endian).  LB_KZG_BAD_SCALAR: the job has a scalar >= r. */
+int lb_kzg_g1_lincomb(lb_ctx* ctx, uint32_t n_jobs, const uint8_t* scalars32, uint8_t* out48, uint8_t* out_status);
 
 /* ---- stage-level entry points (parity tests against the CPU oracle) ----- */
 /* hash_to_G2(msg_i) -> 192-byte uncompressed affine encoding each */
@@ -600,7 +634,8 @@ int lb_sign(lb_ctx* ctx, uint32_t n, const uint8_t* sk32, const uint8_t* message
 /* Per-stage device time (ms) of the last lb_verify_* call, measured with HIP
  * events on the context's stream.  Writes up to max_stages values and their
  * names; returns the number of stages.  A lb_kzg_* call reports kzg_hash,
- * kzg_eval and kzg_tail (those of them it ran). */
+ * kzg_eval and kzg_tail (those of them it ran); a commitment or proof call kzg_hash,
+ * kzg_eval, kzg_quot and kzg_msm (the recoding inside kzg_msm); a G1 load kzg_setup_g1. */
 int lb_last_stage_times(const lb_ctx* ctx, float* out_ms, const char** out_names, int max_stages);
 
 #ifdef __cplusplus

@@ -12,13 +12,13 @@ LIB = os.path.join(HERE, "liblodestar_bls.so")
 # one translation unit per stage group, compiled in parallel and linked into one .so
 UNITS = ["k_final.hip", "k_pairing.hip", "k_aux.hip", "k_hash.hip", "k_miller.hip", "k_scalar.hip", "k_sets.hip",
          "k_smrand.hip", "k_aggsig.hip", "k_prod.hip", "k_tail.hip", "k_ssz.hip", "k_msm.hip", "k_steps.hip", "k_lp.hip",
-         "k_kzg.hip", "lp_blob.hip", "bls_host.hip"]
+         "k_kzg.hip", "k_kzg_msm.hip", "lp_blob.hip", "bls_host.hip"]
 HEADERS = ["bls_kernels.h", "bls_limits.h", "bls_inv.h", "bls_field.h", "bls_fp_ps.h", "bls_fp_pow.h", "bls_curve.h", "bls_hash.h",
            "bls_pairing.h", "bls_wc12.h", "bls_wc12_tables.h", "gen_constants.py", "gen_fp_asm.py", "gen_wc12.py"]
 # headers / generated files only some units depend on (a regenerated program blob must
 # not rebuild every kernel unit)
 UNIT_DEPS = {"k_lp.hip": ["bls_coop.h", "bls_lp.h", "bls_lp_progs.h"], "lp_blob.hip": ["lp_programs.bin"],
-             "k_kzg.hip": ["bls_fr.h", "bls_kzg.h"],
+             "k_kzg.hip": ["bls_fr.h", "bls_kzg.h"], "k_kzg_msm.hip": ["bls_fr.h", "bls_kzg.h"],
              "bls_host.hip": ["bls_lp.h", "bls_lp_progs.h", "bls_fr.h", "bls_kzg.h", "bls_plan.h", "bls_carve.h"]}
 LPGEN = os.path.join(HERE, "lpgen")
 LP_BLOB = os.path.join(CSRC, "lp_programs.bin")
@@ -132,6 +132,9 @@ def kernel_scratch(obj: str) -> dict:
     return out
 
 
+KZG_UNITS = ("k_kzg.hip", "k_kzg_msm.hip")
+
+
 def check_kzg_scratch(obj_dir: str = OBJ_DIR, verbose: bool = False) -> None:
     """The KZG kernels must not raise the private segment ROCr reserves per hardware queue
     (lb_scratch_per_queue): the largest .private_segment_fixed_size among them
@@ -142,12 +145,14 @@ def check_kzg_scratch(obj_dir: str = OBJ_DIR, verbose: bool = False) -> None:
     listed = set(re.findall(r"\(const void\*\)(k_\w+)", body[:body.index("size_t lane = 0;")]))
     ref = 0
     for u in UNITS:
-        if u in ("k_kzg.hip", "bls_host.hip", "lp_blob.hip"):
+        if u in KZG_UNITS + ("bls_host.hip", "lp_blob.hip"):
             continue
         for name, size in kernel_scratch(os.path.join(obj_dir, os.path.splitext(u)[0] + ".o")).items():
             if any("%d%s" % (len(k), k) in name for k in listed if not k.startswith("k_kzg")):
                 ref = max(ref, size)
-    kzg = kernel_scratch(os.path.join(obj_dir, "k_kzg.o"))
+    kzg = {}
+    for u in KZG_UNITS:
+        kzg.update(kernel_scratch(os.path.join(obj_dir, os.path.splitext(u)[0] + ".o")))
     if not kzg or not ref:
         print("check_kzg_scratch: kernel metadata not readable, skipped", flush=True)
         return

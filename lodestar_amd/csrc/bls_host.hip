@@ -227,7 +227,14 @@ struct KzgState {
   g2a* d_neg_tau = nullptr;  // [0]: -[tau]_2 of the loaded setup, [1]: a candidate being checked
   char* d_ws = nullptr;
   size_t ws_cap = 0;
-  hipEvent_t ev[4] = {};
+  hipEvent_t ev[6] = {};
+  // commitments and proofs (k_kzg_msm.hip): the window table of the Lagrange G1 setup,
+  // T[j][i] = [2^(8j)] L[i]; [g1_cur] is the loaded one, the other takes a candidate
+  bool g1_loaded = false;
+  g1a* d_g1_tab[2] = {nullptr, nullptr};
+  int g1_cur = 0;
+  char* d_msm_ws = nullptr;  // the MSM's workspace (LB_KZG_MSM_GROUP jobs), allocated by the first load
+  size_t msm_cap = 0;
 };
 
 struct lb_ctx {
@@ -1370,7 +1377,10 @@ size_t scratch_per_queue(int device, uint32_t* out_lane_bytes) {
                            // (the KZG kernels stay below the pipeline's largest: build.py check_kzg_scratch)
                            (const void*)k_kzg_hash, (const void*)k_kzg_eval, (const void*)k_kzg_decode,
                            (const void*)k_kzg_rho, (const void*)k_kzg_ladder, (const void*)k_kzg_miller,
-                           (const void*)k_kzg_final};
+                           (const void*)k_kzg_final,
+                           (const void*)k_kzg_setup_g1, (const void*)k_kzg_check_com, (const void*)k_kzg_quotient,
+                           (const void*)k_kzg_msm_digits, (const void*)k_kzg_msm_chunks, (const void*)k_kzg_msm_buckets,
+                           (const void*)k_kzg_msm_bits, (const void*)k_kzg_msm_final};
   size_t lane = 0;
   for (const void* k : kernels) {
     hipFuncAttributes a{};
@@ -1683,6 +1693,9 @@ int lb_destroy(lb_ctx* ctx) {
   if (ctx->kzg.d_roots) (void)hipFree(ctx->kzg.d_roots);
   if (ctx->kzg.d_neg_tau) (void)hipFree(ctx->kzg.d_neg_tau);
   if (ctx->kzg.d_ws) (void)hipFree(ctx->kzg.d_ws);
+  if (ctx->kzg.d_msm_ws) (void)hipFree(ctx->kzg.d_msm_ws);
+  for (g1a* t : ctx->kzg.d_g1_tab)
+    if (t) (void)hipFree(t);
   for (hipEvent_t e : ctx->kzg.ev)
     if (e) (void)hipEventDestroy(e);
   {
@@ -3648,6 +3661,250 @@ int lb_kzg_verify_proof_batch(lb_ctx* ctx, uint32_t n, const uint8_t* commitment
   LB_TRY(kzg_finish_verify(ctx, b, n, out_ok, out_status, out_each));
   static const char* const names[] = {"kzg_tail"};
   return kzg_publish_times(ctx, 2, 1, names);
+}
+
+}  // extern "C"
+
+// ============================================================================
+// Blob KZG commitments and proofs (k_kzg_msm.hip)
+// ============================================================================
+namespace {
+
+// device buffers of the fixed-base MSM (a group of LB_KZG_MSM_GROUP jobs) and of a G1 setup
+// load, carved from the MSM workspace; the two lists share it (a load and a call never overlap)
+struct KzgMsmBufs {
+  uint8_t *quot, *out48;
+  uint32_t *keys, *sorted, *hist, *off, *coff, *cursor;
+  g1j *csum, *bsum, *G;
+  // setup load
+  uint8_t *in48, *pt_status;
+  g1j* J;
+};
+
+static_assert(sizeof(g1j) == SZ_G1J, "carve record size");
+
+// The window tables (two: the loaded one and a candidate's) and the MSM workspace, on first use
+int kzg_msm_ensure(lb_ctx* ctx, KzgMsmBufs& m) {
+  KzgState& k = ctx->kzg;
+  constexpr size_t M = LB_KZG_MAX_BLOBS, G = LB_KZG_MSM_GROUP, NB = LB_KZG_MSM_NB;
+  // a call: the quotients and results of all its items, then one group's MSM
+  Carve<11> c;
+  auto quot = c.scratch<uint8_t>(M * LB_KZG_BLOB_BYTES);
+  auto out48 = c.scratch<uint8_t>(M * 48);
+  auto keys = c.scratch<uint32_t>(G * LB_KZG_MSM_ENT);
+  auto sorted = c.scratch<uint32_t>(G * LB_KZG_MSM_ENT);
+  auto hist = c.scratch<uint32_t>(G * NB);
+  auto off = c.scratch<uint32_t>(G * (NB + 1));
+  auto coff = c.scratch<uint32_t>(G * (NB + 1));
+  auto cursor = c.scratch<uint32_t>(G * NB);
+  auto csum = c.scratch<g1j>(G * LB_KZG_MSM_MAXC);
+  auto bsum = c.scratch<g1j>(G * NB);
+  auto Gk = c.scratch<g1j>(G * 8);
+  // a setup load: the file's points, their statuses, the Jacobian multiples before the inversion
+  Carve<3> s;
+  auto in48 = s.scratch<uint8_t>((size_t)LB_KZG_N * 48);
+  auto pt_status = s.scratch<uint8_t>(LB_KZG_N);
+  auto J = s.scratch<g1j>(LB_KZG_MSM_ENT);
+  const size_t call_bytes = c.layout(), load_bytes = s.layout();
+  const size_t bytes = call_bytes > load_bytes ? call_bytes : load_bytes;
+  if (!k.d_msm_ws) {
+    if (hipMalloc(&k.d_msm_ws, bytes) != hipSuccess) {
+      k.d_msm_ws = nullptr;
+      ctx->err = "hipMalloc KZG MSM workspace failed";
+      return LB_ERR_OUT_OF_MEMORY;
+    }
+    k.msm_cap = bytes;
+  }
+  if (!c.fits(k.msm_cap) || !s.fits(k.msm_cap)) {
+    ctx->err = "KZG MSM workspace overflow";
+    return LB_ERR_OUT_OF_MEMORY;
+  }
+  c.bind(k.d_msm_ws);
+  s.bind(k.d_msm_ws);
+  m = KzgMsmBufs{quot, out48, keys, sorted, hist, off, coff, cursor, csum, bsum, Gk, in48, pt_status, J};
+  for (g1a*& t : k.d_g1_tab)
+    if (!t && hipMalloc(&t, sizeof(g1a) * LB_KZG_MSM_ENT) != hipSuccess) {
+      t = nullptr;
+      ctx->err = "hipMalloc KZG G1 table failed";
+      return LB_ERR_OUT_OF_MEMORY;
+    }
+  return LB_OK;
+}
+
+// out48[k] = sum_i scalars[k][i] L[i] for n device-resident jobs, in groups of LB_KZG_MSM_GROUP;
+// a scalar >= r sets status[k] = bad_code (kept when set already); such a job's output is zero
+int kzg_msm(lb_ctx* ctx, const KzgMsmBufs& m, uint32_t n, const uint8_t* scalars, uint8_t* status, uint8_t bad_code,
+            uint8_t* out48) {
+  const g1a* T = ctx->kzg.d_g1_tab[ctx->kzg.g1_cur];
+  for (uint32_t j0 = 0; j0 < n; j0 += LB_KZG_MSM_GROUP) {
+    const uint32_t g = n - j0 < LB_KZG_MSM_GROUP ? n - j0 : LB_KZG_MSM_GROUP;
+    const uint8_t* sc = scalars + (size_t)j0 * LB_KZG_BLOB_BYTES;
+    LB_HIP(hipMemsetAsync(m.hist, 0, sizeof(uint32_t) * g * LB_KZG_MSM_NB, ctx->stream));
+    LB_LAUNCH(k_kzg_msm_digits, (dim3(LB_KZG_N / 256, g)), 256u, sc, status + j0, bad_code, m.keys, m.hist);
+    LB_LAUNCH(k_kzg_msm_scan, g, LB_KZG_MSM_NB, (const uint32_t*)m.hist, m.off, m.coff, m.cursor);
+    LB_LAUNCH(k_kzg_msm_scatter, (dim3(LB_KZG_MSM_ENT / (256 * LB_KZG_MSM_SCAT_PER), g)), 256u,
+              (const uint32_t*)m.keys, (const uint32_t*)m.off, m.cursor, m.sorted);
+    LB_LAUNCH(k_kzg_msm_chunks, (dim3(blocks_for(LB_KZG_MSM_MAXC), g)), TPB, (const uint32_t*)m.off,
+              (const uint32_t*)m.coff, (const uint32_t*)m.sorted, T, m.csum);
+    LB_LAUNCH(k_kzg_msm_buckets, (dim3(LB_KZG_MSM_NB, g)), TPB, (const uint32_t*)m.coff, (const g1j*)m.csum, m.bsum);
+    LB_LAUNCH(k_kzg_msm_bits, (dim3(8, g)), TPB, (const g1j*)m.bsum, m.G);
+    LB_LAUNCH(k_kzg_msm_final, blocks_for(g), TPB, g, (const g1j*)m.G, (const uint8_t*)(status + j0),
+              out48 + (size_t)j0 * 48);
+  }
+  return LB_OK;
+}
+
+// the checks every commitment / proof entry point makes before it touches the device
+int kzg_check_g1_args(lb_ctx* ctx, uint32_t n, bool ptrs_ok, const char* what) {
+  LB_TRY(kzg_check_verify_args(ctx, n, ptrs_ok, what));
+  if (!ctx->kzg.g1_loaded) {
+    ctx->err = std::string(what) + ": no G1 setup loaded (lb_kzg_load_setup_g1)";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  return LB_OK;
+}
+
+// blobs (and commitments or z) up; then the quotients' MSM.  with_hash: z from the transcript
+// (compute_blob_kzg_proof), else z is given (compute_kzg_proof).
+int kzg_prove(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* com48, const uint8_t* z32,
+              uint8_t* out_proofs48, uint8_t* out_y32, uint8_t* out_status) {
+  KzgBufs b;
+  LB_TRY(kzg_ensure(ctx, b));
+  KzgMsmBufs m;
+  LB_TRY(kzg_msm_ensure(ctx, m));
+  KzgState& k = ctx->kzg;
+  LB_KZG_UP(b.blobs, blobs, (size_t)n * LB_KZG_BLOB_BYTES);
+  int first = 1;
+  if (com48) {
+    first = 0;
+    LB_KZG_UP(b.com, com48, (size_t)n * 48);
+    LB_HIP(hipEventRecord(k.ev[0], ctx->stream));
+    LB_LAUNCH(k_kzg_hash, n, LB_KZG_HASH_TPB, (const uint8_t*)b.blobs, (const uint8_t*)b.com, b.z, b.status);
+    LB_LAUNCH(k_kzg_check_com, blocks_for(n), TPB, n, (const uint8_t*)b.com, b.status);
+  } else {
+    LB_KZG_UP(b.z, z32, (size_t)n * 32);
+    LB_HIP(hipMemsetAsync(b.status, 0, n, ctx->stream));
+  }
+  LB_HIP(hipEventRecord(k.ev[1], ctx->stream));
+  LB_LAUNCH(k_kzg_eval, n, LB_KZG_EVAL_TPB, (const uint8_t*)b.blobs, (const fr*)k.d_roots, (const uint8_t*)b.z, b.y,
+            b.status);
+  LB_HIP(hipEventRecord(k.ev[2], ctx->stream));
+  LB_LAUNCH(k_kzg_quotient, n, LB_KZG_EVAL_TPB, (const uint8_t*)b.blobs, (const fr*)k.d_roots, (const uint8_t*)b.z,
+            (const uint8_t*)b.y, (const uint8_t*)b.status, m.quot);
+  LB_HIP(hipEventRecord(k.ev[3], ctx->stream));
+  LB_TRY(kzg_msm(ctx, m, n, m.quot, b.status, LB_KZG_BAD_SCALAR, m.out48));
+  LB_HIP(hipEventRecord(k.ev[4], ctx->stream));
+  LB_HIP(hipMemcpyAsync(out_proofs48, m.out48, (size_t)n * 48, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_y32) LB_HIP(hipMemcpyAsync(out_y32, b.y, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipMemcpyAsync(out_status, b.status, n, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  static const char* const names[] = {"kzg_hash", "kzg_eval", "kzg_quot", "kzg_msm"};
+  return kzg_publish_times(ctx, first, 4 - first, names + first);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lb_kzg_setup_g1_loaded(const lb_ctx* ctx) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  return ctx->kzg.g1_loaded ? 1 : 0;
+}
+
+int lb_kzg_load_setup_g1(lb_ctx* ctx, const uint8_t* g1_lagrange48, int32_t* out_bad_index) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  if (!g1_lagrange48) {
+    ctx->err = "lb_kzg_load_setup_g1: null pointer";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  if (out_bad_index) *out_bad_index = -1;
+  KzgBufs b;
+  LB_TRY(kzg_ensure(ctx, b));
+  KzgMsmBufs m;
+  LB_TRY(kzg_msm_ensure(ctx, m));
+  KzgState& k = ctx->kzg;
+  // the candidate's table is built beside the loaded one and takes its place only when accepted
+  const int cand = k.g1_cur ^ 1;
+  LB_KZG_UP(m.in48, g1_lagrange48, (size_t)LB_KZG_N * 48);
+  LB_HIP(hipEventRecord(k.ev[0], ctx->stream));
+  LB_LAUNCH(k_kzg_setup_g1, blocks_for(LB_KZG_N), TPB, (const uint8_t*)m.in48, m.J, k.d_g1_tab[cand], m.pt_status);
+  LB_HIP(hipEventRecord(k.ev[1], ctx->stream));
+  std::vector<uint8_t> st(LB_KZG_N);
+  LB_HIP(hipMemcpyAsync(st.data(), m.pt_status, LB_KZG_N, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  for (uint32_t i = 0; i < LB_KZG_N; i++) {
+    if (st[i] == LB_ST_OK) continue;
+    if (out_bad_index) *out_bad_index = (int32_t)i;
+    ctx->err = "lb_kzg_load_setup_g1: G1 point " + std::to_string(i) + " of the file " +
+               (st[i] == LB_ST_NOT_IN_GROUP ? "is not in G1"
+                : st[i] == LB_ST_NOT_ON_CURVE ? "is not on the curve"
+                                              : "does not decode");
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  k.g1_cur = cand;
+  k.g1_loaded = true;
+  static const char* const names[] = {"kzg_setup_g1"};
+  return kzg_publish_times(ctx, 0, 1, names);
+}
+
+int lb_kzg_g1_lincomb(lb_ctx* ctx, uint32_t n_jobs, const uint8_t* scalars32, uint8_t* out48, uint8_t* out_status) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  if (n_jobs == 0) return LB_OK;
+  LB_TRY(kzg_check_g1_args(ctx, n_jobs, scalars32 && out48 && out_status, "lb_kzg_g1_lincomb"));
+  KzgBufs b;
+  LB_TRY(kzg_ensure(ctx, b));
+  KzgMsmBufs m;
+  LB_TRY(kzg_msm_ensure(ctx, m));
+  KzgState& k = ctx->kzg;
+  LB_KZG_UP(b.blobs, scalars32, (size_t)n_jobs * LB_KZG_BLOB_BYTES);
+  LB_HIP(hipMemsetAsync(b.status, 0, n_jobs, ctx->stream));
+  LB_HIP(hipEventRecord(k.ev[3], ctx->stream));
+  LB_TRY(kzg_msm(ctx, m, n_jobs, b.blobs, b.status, LB_KZG_BAD_SCALAR, m.out48));
+  LB_HIP(hipEventRecord(k.ev[4], ctx->stream));
+  LB_HIP(hipMemcpyAsync(out48, m.out48, (size_t)n_jobs * 48, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipMemcpyAsync(out_status, b.status, n_jobs, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  static const char* const names[] = {"kzg_msm"};
+  return kzg_publish_times(ctx, 3, 1, names);
+}
+
+int lb_kzg_blob_commitments(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, uint8_t* out_commitments48,
+                            uint8_t* out_status) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  if (n == 0) return LB_OK;
+  LB_TRY(kzg_check_g1_args(ctx, n, blobs && out_commitments48 && out_status, "lb_kzg_blob_commitments"));
+  KzgBufs b;
+  LB_TRY(kzg_ensure(ctx, b));
+  KzgMsmBufs m;
+  LB_TRY(kzg_msm_ensure(ctx, m));
+  KzgState& k = ctx->kzg;
+  // a blob is its polynomial's 4096 scalars as the MSM reads them
+  LB_KZG_UP(b.blobs, blobs, (size_t)n * LB_KZG_BLOB_BYTES);
+  LB_HIP(hipMemsetAsync(b.status, 0, n, ctx->stream));
+  LB_HIP(hipEventRecord(k.ev[3], ctx->stream));
+  LB_TRY(kzg_msm(ctx, m, n, b.blobs, b.status, LB_KZG_BAD_BLOB, m.out48));
+  LB_HIP(hipEventRecord(k.ev[4], ctx->stream));
+  LB_HIP(hipMemcpyAsync(out_commitments48, m.out48, (size_t)n * 48, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipMemcpyAsync(out_status, b.status, n, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  static const char* const names[] = {"kzg_msm"};
+  return kzg_publish_times(ctx, 3, 1, names);
+}
+
+int lb_kzg_blob_proofs(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* commitments48,
+                       uint8_t* out_proofs48, uint8_t* out_status) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  if (n == 0) return LB_OK;
+  LB_TRY(kzg_check_g1_args(ctx, n, blobs && commitments48 && out_proofs48 && out_status, "lb_kzg_blob_proofs"));
+  return kzg_prove(ctx, n, blobs, commitments48, nullptr, out_proofs48, nullptr, out_status);
+}
+
+int lb_kzg_compute_proofs(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* z32, uint8_t* out_proofs48,
+                          uint8_t* out_y32, uint8_t* out_status) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  if (n == 0) return LB_OK;
+  LB_TRY(kzg_check_g1_args(ctx, n, blobs && z32 && out_proofs48 && out_y32 && out_status, "lb_kzg_compute_proofs"));
+  return kzg_prove(ctx, n, blobs, nullptr, z32, out_proofs48, out_y32, out_status);
 }
 
 }  // extern "C"

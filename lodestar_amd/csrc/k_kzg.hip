@@ -29,22 +29,6 @@ LB_DEV uint32_t kzg_domain_word(const char* d, uint32_t j) {
          ((uint32_t)(uint8_t)d[4 * j + 2] << 8) | (uint32_t)(uint8_t)d[4 * j + 3];
 }
 
-// 8 big-endian words (as they lie in a blob) -> raw little-endian limbs
-LB_DEV void kzg_raw_from_words(uint32_t* t, const uint32_t* __restrict__ w) {
-#pragma unroll
-  for (int j = 0; j < 8; j++) t[j] = __builtin_bswap32(w[7 - j]);
-}
-LB_DEV bool kzg_load_fr(fr& r, const uint32_t* __restrict__ w) {
-  uint32_t t[8];
-  kzg_raw_from_words(t, w);
-  const bool ok = fr_raw_is_canonical(t);
-  fr raw;
-#pragma unroll
-  for (int j = 0; j < 8; j++) raw.l[j] = ok ? t[j] : 0u;
-  fr_to_mont(r, raw);
-  return ok;
-}
-
 // ---- setup ------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_kzg_roots(fr* __restrict__ roots) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -123,18 +123,31 @@ export interface GpuBackend {
     commitments: Uint8Array,
     proofs: Uint8Array
   ): Promise<{ok: boolean; status: Uint8Array}>;
+  /** the 4096 G1 Lagrange lines of trusted_setup.txt (48 bytes each, file order); a refused point
+   * rejects with its index in the message and keeps the old table */
+  kzgLoadSetupG1?(g1Lagrange: Uint8Array): Promise<void>;
+  /** blobToKzgCommitment / computeBlobKzgProof / computeKzgProof of n <= 64 items; an item with a
+   * status has all-zero outputs, the others are computed */
+  kzgBlobCommitments?(blobs: Uint8Array): Promise<{commitments: Uint8Array; status: Uint8Array}>;
+  kzgBlobProofs?(blobs: Uint8Array, commitments: Uint8Array): Promise<{proofs: Uint8Array; status: Uint8Array}>;
+  kzgComputeProofs?(blobs: Uint8Array, zs: Uint8Array): Promise<{proofs: Uint8Array; ys: Uint8Array; status: Uint8Array}>;
   close?(): Promise<void>;
 }
 
-/** The verification half of `ckzg` (BN/util/kzg.ts:15-22) on the GPU (kzg.js).  Throws where c-kzg
+/** The blob methods of `ckzg` (BN/util/kzg.ts:15-22) on the GPU (kzg.js).  Throws where c-kzg
  * throws (lengths, a field element >= r, bytes that are no G1 point), false only for a failed
- * pairing check.  The load and verify methods return Promises: the addon never blocks the event
- * loop.  The two compute methods throw "not implemented: use c-kzg". */
+ * pairing check.  Every method but freeTrustedSetup returns a Promise: the addon never blocks the
+ * event loop.  On a backend without kzgBlobCommitments / kzgBlobProofs the two compute methods
+ * throw "not implemented: use c-kzg" synchronously. */
 export interface GpuKzg {
   freeTrustedSetup(): void;
   loadTrustedSetup(filePath: string): Promise<void>;
-  blobToKzgCommitment(blob: Uint8Array): never;
-  computeBlobKzgProof(blob: Uint8Array, commitment: Uint8Array): never;
+  blobToKzgCommitment(blob: Uint8Array): Promise<Uint8Array>;
+  computeBlobKzgProof(blob: Uint8Array, commitment: Uint8Array): Promise<Uint8Array>;
+  blobsToKzgCommitments(blobs: Uint8Array[]): Promise<Uint8Array[]>;
+  computeBlobKzgProofs(blobs: Uint8Array[], commitments: Uint8Array[]): Promise<Uint8Array[]>;
+  /** -> [proof, y] */
+  computeKzgProof(blob: Uint8Array, z: Uint8Array): Promise<[Uint8Array, Uint8Array]>;
   verifyBlobKzgProof(blob: Uint8Array, commitment: Uint8Array, proof: Uint8Array): Promise<boolean>;
   verifyBlobKzgProofBatch(
     blobs: Uint8Array[],
@@ -143,6 +156,7 @@ export interface GpuKzg {
   ): Promise<boolean>;
 }
 export function createGpuKzg(backend: GpuBackend): GpuKzg;
+export function parseTrustedSetupG1(text: string): Uint8Array;
 
 /** verifyAndAggregateSameMessage: the verdicts, and what attestationPool.add would have built from
  * the valid signatures -- their 96-byte compressed sum (null when count is 0) and how many. */

@@ -1,22 +1,27 @@
 "use strict";
-// c-kzg's verification surface on the GPU: an object of the shape of `ckzg` in
+// c-kzg's blob surface on the GPU: an object of the shape of `ckzg` in
 // packages/beacon-node/src/util/kzg.ts:15-22, over an addon Context
-// (kzgLoadSetup / kzgVerifyBlobProofBatch -> lb_kzg_*).
+// (kzgLoadSetup / kzgVerifyBlobProofBatch / kzgLoadSetupG1 / kzgBlobCommitments / kzgBlobProofs /
+// kzgComputeProofs -> lb_kzg_*).
 //
 // The split between throwing and returning false is c-kzg's: malformed input -- wrong
 // lengths, a field element >= r, bytes that are not a point of G1 (C_KZG_BADARGS) --
 // throws; only a failed pairing check gives false
 // (chain/validation/blobSidecar.ts:207-216 reports the two differently).
 //
-// One difference: the addon never blocks the event loop, so loadTrustedSetup and the two
-// verify methods return Promises (c-kzg's are synchronous on the main thread) -- the
-// call sites add an `await`.  blobToKzgCommitment / computeBlobKzgProof are not provided.
+// One difference: the addon never blocks the event loop, so loadTrustedSetup, the two verify
+// methods and blobToKzgCommitment / computeBlobKzgProof / computeKzgProof return Promises
+// (c-kzg's are synchronous on the main thread) -- the call sites add an `await`.  On a backend
+// without the commitment entries the two compute methods throw "not implemented: use c-kzg",
+// synchronously.
 const fs = require("fs");
 const path = require("path");
 
 const BYTES_PER_BLOB = 131072;
 const BYTES_PER_G1 = 48;
 const BYTES_PER_G2 = 96;
+const BYTES_PER_FIELD_ELEMENT = 32;
+const SETUP_G1_POINTS = 4096;
 const MAX_BLOBS_PER_CALL = 64; // LB_KZG_MAX_BLOBS
 const STATUS_NAMES = ["OK", "BAD_BLOB", "BAD_COMMITMENT", "BAD_PROOF", "BAD_SCALAR"];
 
@@ -31,6 +36,24 @@ function parseTrustedSetup(text) {
   const hex = lines[2 + n1 + 1];
   if (!/^[0-9a-fA-F]+$/.test(hex) || hex.length !== 2 * BYTES_PER_G2) throw Error("trusted setup: G2 point 1 is not 96 hex bytes");
   return Uint8Array.from(Buffer.from(hex, "hex"));
+}
+
+// The 4096 G1 Lagrange lines of a trusted_setup.txt, 48 bytes each, in file order (the device
+// applies the bit-reversal permutation of KZG_SETUP_G1_LAGRANGE)
+function parseTrustedSetupG1(text) {
+  parseTrustedSetup(text); // (the counts and the line total)
+  const lines = text.split(/\s+/).filter((x) => x.length > 0);
+  const out = new Uint8Array(SETUP_G1_POINTS * BYTES_PER_G1);
+  for (let i = 0; i < SETUP_G1_POINTS; i++) {
+    const hex = lines[2 + i];
+    if (!/^[0-9a-fA-F]+$/.test(hex) || hex.length !== 2 * BYTES_PER_G1) throw Error(`trusted setup: G1 point ${i} is not 48 hex bytes`);
+    out.set(Buffer.from(hex, "hex"), i * BYTES_PER_G1);
+  }
+  return out;
+}
+
+function split(buf, size, n) {
+  return Array.from({length: n}, (_, i) => Uint8Array.from(buf.subarray(i * size, (i + 1) * size)));
 }
 
 function concat(items, size, what) {
@@ -65,20 +88,69 @@ function createGpuKzg(backend) {
     }
     return ok;
   }
+  // The commitment / proof methods.  The check for the backend's entry is synchronous (a backend
+  // without it throws, it does not reject); lengths and statuses reject before / after the device.
+  function need(method) {
+    if (typeof backend[method] !== "function") throw Error("not implemented: use c-kzg");
+  }
+  // columns: [items, size, name]...; call(joined columns...) per part of at most MAX_BLOBS_PER_CALL
+  // items -> the named output columns, split per item
+  async function inParts(method, columns, outputs) {
+    if (!loaded) throw Error("trusted setup is not loaded");
+    const n = columns[0][0].length;
+    for (const [items] of columns) if (items.length !== n) throw Error("blobs and their companions differ in length");
+    const joined = [];
+    for (let lo = 0; lo < n; lo += MAX_BLOBS_PER_CALL) {
+      const hi = Math.min(n, lo + MAX_BLOBS_PER_CALL);
+      joined.push(columns.map(([items, size, what]) => concat(items.slice(lo, hi), size, what)));
+    }
+    const out = outputs.map(() => []);
+    for (let k = 0; k < joined.length; k++) {
+      const res = await backend[method](...joined[k]);
+      res.status.forEach((st, i) => {
+        if (st !== 0) throw Error(`item ${k * MAX_BLOBS_PER_CALL + i}: ${STATUS_NAMES[st] || st}`);
+      });
+      outputs.forEach(([name, size], j) => out[j].push(...split(res[name], size, res.status.length)));
+    }
+    return out;
+  }
+  function blobsToKzgCommitments(blobs) {
+    need("kzgBlobCommitments");
+    return inParts("kzgBlobCommitments", [[blobs, BYTES_PER_BLOB, "blob"]], [["commitments", BYTES_PER_G1]]).then((o) => o[0]);
+  }
+  function computeBlobKzgProofs(blobs, commitments) {
+    need("kzgBlobProofs");
+    return inParts("kzgBlobProofs", [[blobs, BYTES_PER_BLOB, "blob"], [commitments, BYTES_PER_G1, "commitment"]],
+      [["proofs", BYTES_PER_G1]]).then((o) => o[0]);
+  }
   return {
     async loadTrustedSetup(filePath) {
       if (loaded) throw Error("Error trusted setup is already loaded"); // (util/kzg.ts:80 matches this text)
-      await backend.kzgLoadSetup(parseTrustedSetup(fs.readFileSync(filePath, "utf8")));
+      const text = fs.readFileSync(filePath, "utf8");
+      const tau = parseTrustedSetup(text);
+      // G1 first: a refused G1 point leaves the backend's [tau]_2 as it was
+      if (typeof backend.kzgLoadSetupG1 === "function") await backend.kzgLoadSetupG1(parseTrustedSetupG1(text));
+      await backend.kzgLoadSetup(tau);
       loaded = true;
     },
     freeTrustedSetup() {
       loaded = false;
     },
-    blobToKzgCommitment() {
-      throw Error("not implemented: use c-kzg");
+    blobToKzgCommitment(blob) {
+      need("kzgBlobCommitments");
+      return blobsToKzgCommitments([blob]).then((c) => c[0]);
     },
-    computeBlobKzgProof() {
-      throw Error("not implemented: use c-kzg");
+    computeBlobKzgProof(blob, commitment) {
+      need("kzgBlobProofs");
+      return computeBlobKzgProofs([blob], [commitment]).then((p) => p[0]);
+    },
+    blobsToKzgCommitments,
+    computeBlobKzgProofs,
+    // -> [proof, y], as c-kzg's computeKzgProof
+    computeKzgProof(blob, z) {
+      need("kzgComputeProofs");
+      return inParts("kzgComputeProofs", [[[blob], BYTES_PER_BLOB, "blob"], [[z], BYTES_PER_FIELD_ELEMENT, "z"]],
+        [["proofs", BYTES_PER_G1], ["ys", BYTES_PER_FIELD_ELEMENT]]).then(([p, y]) => [p[0], y[0]]);
     },
     verifyBlobKzgProof(blob, commitment, proof) {
       return verifyBlobKzgProofBatch([blob], [commitment], [proof]);
@@ -91,4 +163,4 @@ function loadAddon() {
   return require(path.join(__dirname, "..", "napi", "lodestar_bls.node"));
 }
 
-module.exports = {createGpuKzg, parseTrustedSetup, loadAddon, BYTES_PER_BLOB, BYTES_PER_G1, BYTES_PER_G2, STATUS_NAMES};
+module.exports = {createGpuKzg, parseTrustedSetup, parseTrustedSetupG1, loadAddon, BYTES_PER_BLOB, BYTES_PER_G1, BYTES_PER_G2, STATUS_NAMES};

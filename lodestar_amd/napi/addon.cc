@@ -37,6 +37,10 @@
 //     .kzgLoadSetup(Uint8Array(96)) -> Promise<void>                  (KZG_SETUP_G2_MONOMIAL[1], compressed)
 //     .kzgVerifyBlobProofBatch(blobs n*131072, commitments n*48, proofs n*48: Uint8Array)
 //         -> Promise<{ok: boolean, status: Uint8Array(n)}>             (verifyBlobKzgProofBatch; status LB_KZG_*)
+//     .kzgLoadSetupG1(Uint8Array(196608)) -> Promise<void>            (the 4096 G1 Lagrange lines, file order)
+//     .kzgBlobCommitments(blobs) -> Promise<{commitments: Uint8Array(n*48), status}>   (blobToKzgCommitment)
+//     .kzgBlobProofs(blobs, commitments) -> Promise<{proofs: Uint8Array(n*48), status}> (computeBlobKzgProof)
+//     .kzgComputeProofs(blobs, zs n*32) -> Promise<{proofs, ys: Uint8Array(n*32), status}> (computeKzgProof)
 //     .syncPubkeys(Uint8Array keys, pkLen) -> Promise<number>          (index2pubkey mirror)
 //     .aggregatePubkeys(Uint8Array n*96 | Uint32Array indices) -> Promise<Uint8Array(96)>
 //     .close() -> Promise<void>                                      (waits for calls in flight)
@@ -170,7 +174,7 @@ void check_offsets(const std::vector<uint32_t>& off, size_t n, uint32_t last, co
 
 // ---- tasks ---------------------------------------------------------------------
 enum class Kind {
-  Verify, Partial, Finish, SameMessage, SyncPubkeys, AggPubkeys, AggSigGroups, GtCheck, KzgLoad, KzgVerify, Close
+  Verify, Partial, Finish, SameMessage, SyncPubkeys, AggPubkeys, AggSigGroups, GtCheck, KzgLoad, KzgVerify, KzgLoadG1, KzgCommit, KzgProve, KzgPoint, Close
 };
 
 struct Task {
@@ -658,6 +662,37 @@ void worker_loop(Context* c) {
         complete(c, t);
         break;
       }
+      case Kind::KzgLoadG1: {
+        int32_t bad = -1;
+        const int rc = lb_kzg_load_setup_g1(c->ctx, t->pubkeys.data(), &bad);
+        if (rc != LB_OK) {
+          fail(t, rc, c->ctx);
+          if (bad >= 0) t->errmsg += " (bad index " + std::to_string(bad) + ")";
+        }
+        complete(c, t);
+        break;
+      }
+      case Kind::KzgCommit:  // blobs in messages; commitments (KzgProve) or z (KzgPoint) in pubkeys
+      case Kind::KzgProve:
+      case Kind::KzgPoint: {
+        const size_t n = t->n_keys ? t->n_keys : 1;
+        t->sst.assign(n, 0);
+        t->out_bytes.assign(n * 48, 0);
+        int rc;
+        if (t->kind == Kind::KzgCommit) {
+          rc = lb_kzg_blob_commitments(c->ctx, t->n_keys, t->messages.data(), t->out_bytes.data(), t->sst.data());
+        } else if (t->kind == Kind::KzgProve) {
+          rc = lb_kzg_blob_proofs(c->ctx, t->n_keys, t->messages.data(), t->pubkeys.data(), t->out_bytes.data(),
+                                  t->sst.data());
+        } else {
+          t->valid.assign(n * 32, 0);
+          rc = lb_kzg_compute_proofs(c->ctx, t->n_keys, t->messages.data(), t->pubkeys.data(), t->out_bytes.data(),
+                                     t->valid.data(), t->sst.data());
+        }
+        if (rc != LB_OK) fail(t, rc, c->ctx);
+        complete(c, t);
+        break;
+      }
       case Kind::Close: {
         for (Task* w : prio) {
           const int rc = lb_wait(c->ctx, w->ticket, &w->stats);
@@ -842,6 +877,19 @@ void call_js(napi_env env, napi_value /*cb*/, void* context, void* data) {
         napi_set_named_property(env, result, "status", make_u8(env, t->sst.data(), t->n_keys));
         break;
       }
+      case Kind::KzgLoadG1:
+        napi_get_undefined(env, &result);
+        break;
+      case Kind::KzgCommit:
+      case Kind::KzgProve:
+      case Kind::KzgPoint:
+        napi_create_object(env, &result);
+        napi_set_named_property(env, result, t->kind == Kind::KzgCommit ? "commitments" : "proofs",
+                                make_u8(env, t->out_bytes.data(), (size_t)t->n_keys * 48));
+        if (t->kind == Kind::KzgPoint)
+          napi_set_named_property(env, result, "ys", make_u8(env, t->valid.data(), (size_t)t->n_keys * 32));
+        napi_set_named_property(env, result, "status", make_u8(env, t->sst.data(), t->n_keys));
+        break;
       case Kind::Close:
         napi_get_undefined(env, &result);
         break;
@@ -1164,6 +1212,64 @@ napi_value KzgVerifyBlobProofBatch(napi_env env, napi_callback_info info) {
   return submit(env, c, t);
 }
 
+// kzgLoadSetupG1(g1Lagrange: Uint8Array(4096 x 48)): the G1 lines of trusted_setup.txt, file order; a
+// refused point rejects with its index in the message
+napi_value KzgLoadSetupG1(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  Context* c = unwrap(env, info, &argc, argv);
+  Task* t = new Task();
+  t->kind = Kind::KzgLoadG1;
+  try {
+    if (!c || argc < 1) throw ArgError{"kzgLoadSetupG1(g1Lagrange: Uint8Array(196608))"};
+    typed(env, argv[0], napi_uint8_array, "g1Lagrange", t->pubkeys);
+    if (t->pubkeys.size() != 4096 * 48) throw ArgError{"g1Lagrange: 196608 bytes"};
+  } catch (const ArgError& e) {
+    delete t;
+    return rejected(env, e.msg);
+  }
+  return submit(env, c, t);
+}
+
+// kzgBlobCommitments(blobs) / kzgBlobProofs(blobs, commitments: n x 48) / kzgComputeProofs(blobs, zs: n x 32)
+//   -> Promise<{commitments | proofs: Uint8Array(n x 48), [ys: Uint8Array(n x 32),] status: Uint8Array(n)}>
+// (an item with a status has all-zero outputs)
+napi_value kzg_compute(napi_env env, napi_callback_info info, Kind kind, size_t second, const char* usage,
+                       const char* second_name, const char* second_rule) {
+  size_t argc = 2;
+  napi_value argv[2];
+  Context* c = unwrap(env, info, &argc, argv);
+  Task* t = new Task();
+  t->kind = kind;
+  try {
+    if (!c || argc < (second ? 2u : 1u)) throw ArgError{usage};
+    typed(env, argv[0], napi_uint8_array, "blobs", t->messages);
+    if (t->messages.size() % LB_KZG_BLOB_BYTES) throw ArgError{"blobs: 131072 bytes each"};
+    t->n_keys = (uint32_t)(t->messages.size() / LB_KZG_BLOB_BYTES);
+    if (t->n_keys > LB_KZG_MAX_BLOBS) throw ArgError{"blobs: more than LB_KZG_MAX_BLOBS"};
+    if (second) {
+      typed(env, argv[1], napi_uint8_array, second_name, t->pubkeys);
+      if (t->pubkeys.size() != (size_t)t->n_keys * second) throw ArgError{second_rule};
+    }
+    for (auto* v : {&t->messages, &t->pubkeys}) if (v->empty()) v->push_back(0);
+  } catch (const ArgError& e) {
+    delete t;
+    return rejected(env, e.msg);
+  }
+  return submit(env, c, t);
+}
+napi_value KzgBlobCommitments(napi_env env, napi_callback_info info) {
+  return kzg_compute(env, info, Kind::KzgCommit, 0, "kzgBlobCommitments(blobs: Uint8Array)", "", "");
+}
+napi_value KzgBlobProofs(napi_env env, napi_callback_info info) {
+  return kzg_compute(env, info, Kind::KzgProve, 48, "kzgBlobProofs(blobs, commitments: Uint8Array)", "commitments",
+                     "commitments: 48 bytes per blob");
+}
+napi_value KzgComputeProofs(napi_env env, napi_callback_info info) {
+  return kzg_compute(env, info, Kind::KzgPoint, 32, "kzgComputeProofs(blobs, zs: Uint8Array)", "zs",
+                     "zs: 32 bytes per blob");
+}
+
 napi_value Close(napi_env env, napi_callback_info info) {
   size_t argc = 0;
   Context* c = unwrap(env, info, &argc, nullptr);
@@ -1321,6 +1427,10 @@ napi_value Init(napi_env env, napi_value exports) {
       {"aggregateSignatureGroups", nullptr, AggregateSignatureGroups, nullptr, nullptr, nullptr, napi_default,
        nullptr},
       {"kzgLoadSetup", nullptr, KzgLoadSetup, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"kzgLoadSetupG1", nullptr, KzgLoadSetupG1, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"kzgBlobCommitments", nullptr, KzgBlobCommitments, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"kzgBlobProofs", nullptr, KzgBlobProofs, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"kzgComputeProofs", nullptr, KzgComputeProofs, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"kzgVerifyBlobProofBatch", nullptr, KzgVerifyBlobProofBatch, nullptr, nullptr, nullptr, napi_default,
        nullptr},
       {"close", nullptr, Close, nullptr, nullptr, nullptr, napi_default, nullptr},

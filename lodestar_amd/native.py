@@ -46,6 +46,8 @@ EXPORTED_SYMBOLS = (
     "lb_verify_same_message_batch_agg", "lb_verify_same_message_batch_agg_async", "lb_aggregate_signature_groups",
     "lb_kzg_load_setup", "lb_kzg_setup_loaded", "lb_kzg_verify_blob_proof_batch", "lb_kzg_verify_proof_batch",
     "lb_kzg_blob_challenges", "lb_kzg_evaluate",
+    "lb_kzg_load_setup_g1", "lb_kzg_setup_g1_loaded", "lb_kzg_blob_commitments", "lb_kzg_blob_proofs",
+    "lb_kzg_compute_proofs", "lb_kzg_g1_lincomb",
 )
 
 # blob KZG proof verification (lb_kzg_*)
@@ -202,6 +204,12 @@ def load_library() -> ctypes.CDLL:
     lib.lb_kzg_verify_proof_batch.argtypes = [vp, u32, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int32), vp, vp]
     lib.lb_kzg_blob_challenges.argtypes = [vp, u32, vp, vp, vp, vp, vp]
     lib.lb_kzg_evaluate.argtypes = [vp, u32, vp, vp, vp, vp]
+    lib.lb_kzg_load_setup_g1.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int32)]
+    lib.lb_kzg_setup_g1_loaded.argtypes = [vp]
+    lib.lb_kzg_blob_commitments.argtypes = [vp, u32, vp, vp, vp]
+    lib.lb_kzg_blob_proofs.argtypes = [vp, u32, vp, vp, vp, vp]
+    lib.lb_kzg_compute_proofs.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+    lib.lb_kzg_g1_lincomb.argtypes = [vp, u32, vp, vp, vp]
     lib.lb_set_same_message_mode.argtypes = [vp, u32]
     lib.lb_same_message_mode.argtypes = [vp]
     lib.lb_same_message_aggregates.argtypes = [vp, ctypes.POINTER(_SameMessageBatch), vp, vp, vp]
@@ -980,6 +988,73 @@ class Device:
         st = np.zeros(max(n, 1), np.uint8)
         self._check(self.lib.lb_kzg_evaluate(self._h, n, _ptr(bl), _ptr(z), _ptr(y), _ptr(st)), "lb_kzg_evaluate")
         return [y[32 * i:32 * i + 32].tobytes() for i in range(n)], [int(x) for x in st[:n]]
+
+    # -- blob KZG commitments and proofs ------------------------------------------
+    def kzg_load_setup_g1(self, g1_lagrange: bytes) -> None:
+        """Load the 4096 compressed G1 Lagrange points of a trusted setup, in file order, and build
+        the MSM's window table; a refused point keeps the old table, and the error raised carries
+        its index in file order as ``bad_index``."""
+        a = self._kzg_join([g1_lagrange], 4096 * 48, "g1_lagrange")
+        bad = ctypes.c_int32(-1)
+        try:
+            self._check(self.lib.lb_kzg_load_setup_g1(self._h, _ptr(a), ctypes.byref(bad)), "lb_kzg_load_setup_g1")
+        except LodestarBlsError as e:
+            e.bad_index = int(bad.value)
+            raise
+
+    def kzg_setup_g1_loaded(self) -> bool:
+        return int(self.lib.lb_kzg_setup_g1_loaded(self._h)) == 1
+
+    @staticmethod
+    def _kzg_split(a: np.ndarray, n: int, size: int) -> List[bytes]:
+        return [a[size * i:size * (i + 1)].tobytes() for i in range(n)]
+
+    def kzg_blob_commitments(self, blobs: Sequence[bytes]):
+        """-> (commitments[n], statuses[n]): blob_to_kzg_commitment, 48 bytes each."""
+        n = len(blobs)
+        bl = self._kzg_join(blobs, LB_KZG_BLOB_BYTES, "blob")
+        out = np.zeros(max(n, 1) * 48, np.uint8)
+        st = np.zeros(max(n, 1), np.uint8)
+        self._check(self.lib.lb_kzg_blob_commitments(self._h, n, _ptr(bl), _ptr(out), _ptr(st)),
+                    "lb_kzg_blob_commitments")
+        return self._kzg_split(out, n, 48), [int(x) for x in st[:n]]
+
+    def kzg_blob_proofs(self, blobs: Sequence[bytes], commitments: Sequence[bytes]):
+        """-> (proofs[n], statuses[n]): compute_blob_kzg_proof, 48 bytes each."""
+        n = len(blobs)
+        if len(commitments) != n:
+            raise ValueError("blobs and commitments differ in length")
+        bl = self._kzg_join(blobs, LB_KZG_BLOB_BYTES, "blob")
+        c = self._kzg_join(commitments, 48, "commitment")
+        out = np.zeros(max(n, 1) * 48, np.uint8)
+        st = np.zeros(max(n, 1), np.uint8)
+        self._check(self.lib.lb_kzg_blob_proofs(self._h, n, _ptr(bl), _ptr(c), _ptr(out), _ptr(st)),
+                    "lb_kzg_blob_proofs")
+        return self._kzg_split(out, n, 48), [int(x) for x in st[:n]]
+
+    def kzg_compute_proofs(self, blobs: Sequence[bytes], zs: Sequence[bytes]):
+        """-> (proofs[n], y[n], statuses[n]): compute_kzg_proof(blob_i, z_i)."""
+        n = len(blobs)
+        if len(zs) != n:
+            raise ValueError("blobs and z differ in length")
+        bl = self._kzg_join(blobs, LB_KZG_BLOB_BYTES, "blob")
+        z = self._kzg_join(zs, 32, "z")
+        out = np.zeros(max(n, 1) * 48, np.uint8)
+        y = np.zeros(max(n, 1) * 32, np.uint8)
+        st = np.zeros(max(n, 1), np.uint8)
+        self._check(self.lib.lb_kzg_compute_proofs(self._h, n, _ptr(bl), _ptr(z), _ptr(out), _ptr(y), _ptr(st)),
+                    "lb_kzg_compute_proofs")
+        return self._kzg_split(out, n, 48), self._kzg_split(y, n, 32), [int(x) for x in st[:n]]
+
+    def kzg_g1_lincomb(self, jobs: Sequence[bytes]):
+        """-> (points[n], statuses[n]): sum_i s_i L[i] over the loaded G1 setup (spec order); a job
+        is 4096 big-endian 32-byte scalars."""
+        n = len(jobs)
+        sc = self._kzg_join(jobs, LB_KZG_BLOB_BYTES, "scalars")
+        out = np.zeros(max(n, 1) * 48, np.uint8)
+        st = np.zeros(max(n, 1), np.uint8)
+        self._check(self.lib.lb_kzg_g1_lincomb(self._h, n, _ptr(sc), _ptr(out), _ptr(st)), "lb_kzg_g1_lincomb")
+        return self._kzg_split(out, n, 48), [int(x) for x in st[:n]]
 
     def set_latency_path(self, max_sets: int) -> None:
         """Calls of at most max_sets sets take the latency path (0: never)."""
