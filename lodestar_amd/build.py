@@ -19,7 +19,8 @@ HEADERS = ["bls_kernels.h", "bls_limits.h", "bls_inv.h", "bls_field.h", "bls_fp_
 # not rebuild every kernel unit)
 UNIT_DEPS = {"k_lp.hip": ["bls_coop.h", "bls_lp.h", "bls_lp_progs.h"], "lp_blob.hip": ["lp_programs.bin"],
              "k_kzg.hip": ["bls_fr.h", "bls_kzg.h"], "k_kzg_msm.hip": ["bls_fr.h", "bls_kzg.h"],
-             "bls_host.hip": ["bls_lp.h", "bls_lp_progs.h", "bls_fr.h", "bls_kzg.h", "bls_plan.h", "bls_carve.h"]}
+             "bls_host.hip": ["bls_lp.h", "bls_lp_progs.h", "bls_fr.h", "bls_kzg.h", "bls_plan.h", "bls_ctx_plan.h",
+                              "bls_carve.h"]}
 LPGEN = os.path.join(HERE, "lpgen")
 LP_BLOB = os.path.join(CSRC, "lp_programs.bin")
 SOURCES = UNITS + HEADERS + ["bls_all.hip"] + sorted({d for v in UNIT_DEPS.values() for d in v})

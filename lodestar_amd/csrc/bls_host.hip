@@ -47,6 +47,7 @@
 #include "bls_kernels.h"
 #include "bls_kzg.h"
 #include "bls_lp.h"
+#include "bls_ctx_plan.h"
 #include "bls_plan.h"
 #ifdef LB_LP_PROGS_HEADER  // (a variant's programs, tools/lp_rows_variant.py)
 #include LB_LP_PROGS_HEADER
@@ -131,8 +132,9 @@ struct SmState {
 // One in-flight call: two streams (DAG), own workspace, staging and events.
 struct Slot {
   hipStream_t st[2] = {};
-  // LB_PRIO_CUS with LB_PRIO_DYN=1: the slot's streams without and with the CU mask;
-  // st[] is one pair or the other, chosen when a call is submitted (pick_streams)
+  // the slot's streams without and with the CU mask, as the context's plan has them
+  // (bls_ctx_plan.h StreamPlan); st[] is one pair or the other, chosen when a call is
+  // submitted (pick_streams, LB_PRIO_DYN)
   hipStream_t st_full[2] = {}, st_mask[2] = {};
   hipEvent_t dep[8] = {};
   hipEvent_t done = nullptr;
@@ -240,29 +242,18 @@ struct KzgState {
 struct lb_ctx {
   int device = -1;
   KzgState kzg;
-  // One single-stream slot per hardware queue HIP gives this process: GPU_MAX_HW_QUEUES
-  // (HIP's default and the box's setting are 4; at most kMaxSlots) -- more streams than
-  // queues share a queue and measured -20 %, profiles/ab_r01i.txt.  That many calls are
-  // in flight on the async API; a synchronous call runs on slot 0 as the two-stream DAG
-  // by borrowing slot 1's stream for its duration.  LB_SLOTS overrides the count.
-  // (24 hardware queues failed: HSA_STATUS_ERROR_OUT_OF_RESOURCES at k_miller_acc's dispatch,
-  // whose 3.3 KB/lane private segment is reserved per queue; profiles/ab_r03/r03g_q24_fail.txt)
-  static constexpr int kMaxSlots = 16;
-  int n_slots = 4;
-  int streams_per_slot[kMaxSlots + 1] = {2};  // (set for every slot in lb_create)
-  // slots[n_slots] is the priority lane: one stream at the device's highest
+  // the context's switches and every decision taken from them at creation (bls_ctx_plan.h):
+  // slots, streams, CU mask, hardware queues.  plan.n_slots calls are in flight on the async
+  // API; a synchronous call runs on slot 0 as the two-stream DAG by borrowing slot 1's stream
+  // for its duration.
+  CtxConfig ccfg;
+  CtxPlan plan;
+  // slots[plan.n_slots] is the priority lane: one stream at the device's highest
   // priority, outside the async round robin, for latency-critical calls
   // (lb_verify_requests_priority_async, and lb_verify_requests of at most
   // lp_max_sets sets): they never queue behind the calls in flight
-  Slot slots[kMaxSlots + 1];
-  Slot& prio() { return slots[n_slots]; }
-  bool prio_kcopy = true;  // the priority slot's host copies as kernels (slot_copy, LB_PRIO_KCOPY)
-  int prio_cus = 0;  // CUs the throughput slots leave to the priority lane (LB_PRIO_CUS)
-  // LB_PRIO_DYN=1 (with LB_PRIO_CUS): the throughput calls take the masked streams only
-  // while the priority lane has been used within the last prio_hold_ms (LB_PRIO_HOLD_MS)
-  bool prio_dyn = false;
-  int prio_dyn_slots = 0;  // slots [0, prio_dyn_slots) own masked streams (LB_PRIO_DYN_SLOTS)
-  double prio_hold_ms = 250.0;
+  Slot slots[kCtxMaxSlots + 1];
+  Slot& prio() { return slots[plan.n_slots]; }
   // steady-clock ns of the priority lane's last use (or lb_mark_priority from another
   // thread: an atomic, the one field of a context another thread may write)
   std::atomic<int64_t> last_prio_ns{INT64_MIN / 2};
@@ -274,26 +265,15 @@ struct lb_ctx {
   uint64_t two_phase[kTwoPhaseRing] = {};
   int two_phase_pos = 0;
   // (LB_TP_RELEASE: cfg.tp_release / cfg.tp_release_cfg; one record per two-phase ticket, ring by ticket)
-  uint32_t tp_pause = 0;
-  uint32_t tp_pause_calls = 32;  // (LB_TP_PAUSE; 0: always release)
-  bool fault_rerun = false;  // LB_FAULT_RERUN=1 (tests only): a failed combine's re-run fails to submit
+  uint32_t tp_pause = 0;  // two-phase calls still to run in the legacy mode (ccfg.tp_pause after a failed combine)
   TwoPhaseRec tp[kTwoPhaseRing];
   ErrorText err;
   hipStream_t stream = nullptr;  // slot 0 stream 0 (synchronous helper calls)
   // the switches that shape a pipeline call (bls_plan.h: plan_pipeline reads nothing else)
   PipeConfig cfg;
-  // LB_DAG=0: a call never borrows a second stream (every kernel of a lone call runs
-  // alone on the GPU: bench.py's per-kernel iso timings and their rocprof profile)
-  bool dag = true;
-  // LB_STAGE_EVENTS=0: no per-stage timing events (two HIP calls per kernel of the
-  // submission; the N-API addon sets it, lb_last_stage_times is then empty)
-  bool stage_events = true;
-  // same-message packages of at most LB_SM_DEC_MAX signatures decode them as round programs
-  // (k_lp_dec; LB_SM_LP_DECODE=0: k_decode_sigs always)
-  bool sm_lp_decode = true;
   // same-message aggregation of the packages submitted from now on: LB_SM_PLAIN (plain sums, the
   // reference snapshot's) or LB_SM_RANDOMIZED (sum s_i pk_i / sum s_i sig_i, k_smrand.hip);
-  // lb_set_same_message_mode, or LB_SM_RANDOMIZED=1 in the environment at lb_create
+  // lb_set_same_message_mode; ccfg.sm_randomized at lb_create
   uint32_t sm_mode = LB_SM_PLAIN;
   // device-resident pubkey table (index2pubkey mirror, lb_pubkey_table_*)
   g1a* d_table = nullptr;
@@ -311,7 +291,7 @@ struct lb_ctx {
   // shards' partials never drains the slots' calls in flight
   hipStream_t aux_stream = nullptr;
   // the merged check's one-wave chain of every slot (highest priority) when
-  // LB_TAIL_PRIO=1; nullptr (default): the slot's own stream
+  // plan.tail_stream; nullptr (default): the slot's own stream
   hipStream_t tail_stream = nullptr;
   uint8_t* d_aux = nullptr;
   uint8_t* h_aux = nullptr;
@@ -319,10 +299,6 @@ struct lb_ctx {
   // latency path: the round programs in device memory (uploaded on first use);
   // calls of at most cfg.lp_max_sets sets run it instead of the throughput pipeline
   uint32_t* d_lp = nullptr;
-  bool gt_lp = true;  // lb_gt_check's final exponentiation as a round program (LB_GT_LP=0: one wave)
-  int hw_queues = 0;  // hardware queues this context opens (priced by lb_create's guard)
-  int q_plain = 0, q_high = 0, q_masked = 0;  // its streams in the process tally (g_q_*)
-  bool lane = false;  // lb_create_lane: a latency-lane context (one slot, no CU-masked streams)
   int last_call_streams = 0;  // streams of the last submitted verify call (begin_call)
   unsigned long long lp_clk[4] = {};  // clock stamps of the last retired latency-path call
 };
@@ -403,7 +379,7 @@ int ensure_pin(lb_ctx* ctx, Slot& sl, size_t bytes) {
 // Launch `kern` on stream `s` of slot `sl`, bracketed by timing events.
 #define LB_STAGE_ON(name, strm, kern, grid, block, ...)                                    \
   do {                                                                                     \
-    const int si_ = (ctx->stage_events && sl.n_stages < Slot::kMaxStages) ? sl.n_stages++ : -1; \
+    const int si_ = (ctx->ccfg.stage_events && sl.n_stages < Slot::kMaxStages) ? sl.n_stages++ : -1; \
     hipStream_t strm_ = (strm);                                                            \
     LB_COUNT_SYNC();                                                                       \
     if (si_ >= 0) {                                                                        \
@@ -553,14 +529,14 @@ int run_tails(lb_ctx* ctx, Slot& sl) {
 }
 
 static bool any_slot_busy(const lb_ctx* ctx) {
-  for (int s = 0; s <= ctx->n_slots; s++)
+  for (int s = 0; s <= ctx->plan.n_slots; s++)
     if (ctx->slots[s].busy) return true;
   return false;
 }
 
 // the GPU is this call's: no other throughput slot busy, the slots lent to the call apart
 static bool call_is_lone(const lb_ctx* ctx, const Slot& sl) {
-  for (int s = 0; s < ctx->n_slots; s++)
+  for (int s = 0; s < ctx->plan.n_slots; s++)
     if (&ctx->slots[s] != &sl && ctx->slots[s].busy && ctx->slots[s].lent_to != &sl) return false;
   return true;
 }
@@ -1137,7 +1113,7 @@ int validate_batch(lb_ctx* ctx, const lb_request_batch* b) {
 // calls' staging; elsewhere hipMemcpyAsync.  Host buffers are pinned (hipHostMalloc).
 int slot_copy(lb_ctx* ctx, Slot& sl, void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t st) {
   if (!n) return LB_OK;
-  if (ctx->prio_kcopy && &sl == &ctx->prio() && n < (1u << 30)) {
+  if (ctx->ccfg.prio_kcopy && &sl == &ctx->prio() && n < (1u << 30)) {
     const size_t blocks = (n / 16 + 255) / 256;
     LB_ENQUEUE(st, k_copy_bytes, blocks < 1 ? 1 : blocks > 512 ? 512 : (unsigned)blocks, 256, (const uint8_t*)src,
                (uint8_t*)dst, (uint32_t)n);
@@ -1251,9 +1227,9 @@ int finish_slot(lb_ctx* ctx, Slot& sl) {
 // the signature / MSM branch), so it borrows an idle slot's stream; the next call
 // that wants that slot waits for this one first (finish_slot).
 void borrow_idle_stream(lb_ctx* ctx, Slot& sl) {
-  if (!ctx->dag || sl.st[1] != sl.st[0] || sl.borrowed || &sl == &ctx->prio()) return;
+  if (!ctx->ccfg.dag || sl.st[1] != sl.st[0] || sl.borrowed || &sl == &ctx->prio()) return;
   Slot* idle = nullptr;
-  for (int s = 0; s < ctx->n_slots; s++) {
+  for (int s = 0; s < ctx->plan.n_slots; s++) {
     Slot& o = ctx->slots[s];
     if (&o == &sl) continue;
     if (o.busy || o.partial_pending) return;  // not alone on the GPU
@@ -1290,7 +1266,7 @@ int end_call_async(lb_ctx* ctx, Slot& sl) {
 }
 
 Slot* slot_of_ticket(lb_ctx* ctx, uint64_t ticket) {
-  for (int s = 0; s <= ctx->n_slots; s++)
+  for (int s = 0; s <= ctx->plan.n_slots; s++)
     if (ctx->slots[s].busy && ctx->slots[s].ticket == ticket) return &ctx->slots[s];
   return nullptr;
 }
@@ -1311,7 +1287,7 @@ struct BorrowGuard {
 };
 int borrow_second_stream(lb_ctx* ctx, BorrowGuard& g) {
   Slot& s0 = ctx->slots[0];
-  if (ctx->dag && ctx->streams_per_slot[0] == 1 && ctx->n_slots >= 2) {
+  if (ctx->ccfg.dag && ctx->plan.streams_per_slot[0] == 1 && ctx->plan.n_slots >= 2) {
     LB_TRY(finish_slot(ctx, ctx->slots[1]));
     s0.st[1] = s0.guard_st = ctx->slots[1].st[0];
     g.active = true;
@@ -1321,7 +1297,7 @@ int borrow_second_stream(lb_ctx* ctx, BorrowGuard& g) {
 
 // Idle slot 0 for the synchronous helper entry points.
 int helper_slot(lb_ctx* ctx) {
-  for (int i = 0; i <= ctx->n_slots; i++) LB_TRY(finish_slot(ctx, ctx->slots[i]));
+  for (int i = 0; i <= ctx->plan.n_slots; i++) LB_TRY(finish_slot(ctx, ctx->slots[i]));
   return LB_OK;
 }
 
@@ -1351,16 +1327,12 @@ int lb_device_count(void) {
   return n;
 }
 
-// Private-segment (scratch) reservation of one HIP hardware queue.  ROCr backs a
-// queue's scratch for a dispatch at full-device occupancy: private bytes per lane
-// x 64 lanes x 32 waves per CU x CUs, and keeps it for the queue's lifetime, so a
-// process with Q queues that run the pipeline's largest-scratch kernel reserves Q
-// times that.  At 24 queues the first 65,536-set calls failed with
-// HSA_STATUS_ERROR_OUT_OF_RESOURCES (profiles/ab_r03/r03g_q24_fail.txt) with the
-// HBM otherwise free; 16 ran, which is the cap lb_create enforces.
 static std::string g_create_err = "null context";
 
-size_t scratch_per_queue(int device, uint32_t* out_lane_bytes) {
+// The device as plan_context needs it -- the largest private segment of the kernels a queue
+// may run, and the CU count -- and the scratch one hardware queue reserves for them
+// (queue_scratch_bytes, bls_ctx_plan.h).
+size_t scratch_per_queue(int device, DeviceFacts* out_facts) {
   const void* kernels[] = {(const void*)k_miller_acc<16>, (const void*)k_miller_acc<32>,
                            (const void*)k_miller_acc<64>, (const void*)k_step_acc<0, 1>,
                            (const void*)k_step_acc<0, 2>, (const void*)k_step_acc<1, 1>, (const void*)k_step_acc<2, 1>, (const void*)k_step_acc<2, 2>, (const void*)k_lines<1>,
@@ -1386,204 +1358,64 @@ size_t scratch_per_queue(int device, uint32_t* out_lane_bytes) {
     hipFuncAttributes a{};
     if (hipFuncGetAttributes(&a, k) == hipSuccess && a.localSizeBytes > lane) lane = a.localSizeBytes;
   }
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 256;
-  if (out_lane_bytes) *out_lane_bytes = (uint32_t)lane;
-  return lane * 64 * 32 * (size_t)cus;
+  DeviceFacts f;
+  f.lane_bytes = (uint32_t)lane;
+  if (hipDeviceGetAttribute(&f.cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) f.cus = 0;
+  if (out_facts) *out_facts = f;
+  return queue_scratch_bytes(f);
 }
 
-// The streams of every live context of this process, by kind: HIP pools the
-// plain streams of one priority into at most GPU_MAX_HW_QUEUES queues PER PROCESS, so a
-// second context's plain and high-priority streams share the first one's queues (up to
-// that cap) while each CU-masked stream takes a queue of its own.  A latency-lane context
-// (lb_create_lane, optional: the addon runs without one) is priced on the process total
-// against kProcessQueueBudget, the largest process configuration seen to run: bench.py's
-// process and the node addon's, 16 plain + 2 CU-masked + 4 high-priority queues (the main
-// context's priority lane and aux stream, and the second context's two).
+// The streams of every live context of this process, by kind (QueueTally, bls_ctx_plan.h).
 static std::mutex g_q_mu;
-static int g_q_plain = 0, g_q_high = 0, g_q_masked = 0;
-static constexpr int kProcessQueueBudget = 22;
+static QueueTally g_q;
 
-static int pooled_queues(int plain, int high, int masked, int maxq) {
-  return (plain < maxq ? plain : maxq) + (high < maxq ? high : maxq) + masked;
-}
+static const char* env_lookup(const char* name) { return getenv(name); }
 
+// Facts, plan, resources: the switches and the device, every decision (plan_context: no HIP
+// object exists when it refuses), then exactly the streams the plan priced.
 static int create_ctx(int device, lb_ctx** out_ctx, bool lane) {
   if (!out_ctx) return LB_ERR_INVALID_ARGUMENT;
   *out_ctx = nullptr;
-  const bool lane_ctx = lane;  // (the queue guard's block below has a `lane` of its own: bytes per lane)
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0 || device < 0 || device >= n) return LB_ERR_NO_DEVICE;
+  bool ok = hipSetDevice(device) == hipSuccess;
+  CtxConfig ccfg;
+  ctx_config_from_env(ccfg, env_lookup);
+  DeviceFacts dev;
+  (void)scratch_per_queue(device, &dev);
+  CtxPlan plan;
+  {
+    std::lock_guard<std::mutex> g(g_q_mu);
+    plan = plan_context(ccfg, dev, lane, g_q);
+    if (plan.err) {
+      g_create_err = plan.msg;
+      return plan.err;
+    }
+    g_q.plain += plan.q_plain;
+    g_q.high += plan.q_high;
+    g_q.masked += plan.q_masked;
+  }
   lb_ctx* ctx = new lb_ctx();
   ctx->device = device;
-  ctx->lane = lane;
-  bool ok = hipSetDevice(device) == hipSuccess;
-  // one single-stream slot per hardware queue HIP gives this process (4 by
-  // default; a host that sets GPU_MAX_HW_QUEUES=8 before HIP starts gets 8 calls
-  // in flight: 2.94 vs 2.74 M sets/s once the merged check's one-wave kernels
-  // left each call's queue idle at its end, profiles/ab_r03/hwq; up to 16)
-  if (const char* e = getenv("GPU_MAX_HW_QUEUES")) {
-    const int v = atoi(e);
-    if (v > lb_ctx::kMaxSlots) {
-      uint32_t lane = 0;
-      const size_t per_q = scratch_per_queue(device, &lane);
-      char msg[320];
-      snprintf(msg, sizeof msg,
-               "GPU_MAX_HW_QUEUES=%d exceeds %d: %u private bytes per lane reserve %.2f GB of scratch per "
-               "hardware queue (%.1f GB for %d queues); 24 queues failed with HSA_STATUS_ERROR_OUT_OF_RESOURCES",
-               v, lb_ctx::kMaxSlots, lane, per_q / 1e9, per_q * (double)v / 1e9, v);
-      g_create_err = msg;
-      delete ctx;
-      return LB_ERR_RESOURCES;
-    }
-    ctx->n_slots = v < 4 ? 4 : v;
-  }
-  if (const char* e = getenv("LB_SLOTS")) {
-    const int v = atoi(e);
-    if (v >= 1 && v <= lb_ctx::kMaxSlots) ctx->n_slots = v;
-  }
-  if (lane) ctx->n_slots = 1;  // a latency-lane context: its priority lane (+ one slot for helpers)
-  config_from_env(ctx->cfg, [](const char* name) -> const char* { return getenv(name); });
-  if (const char* e = getenv("LB_SM_LP_DECODE")) ctx->sm_lp_decode = atoi(e) != 0;
-  if (const char* e = getenv("LB_SM_RANDOMIZED")) ctx->sm_mode = atoi(e) == 1 ? LB_SM_RANDOMIZED : LB_SM_PLAIN;
-  if (const char* e = getenv("LB_TP_PAUSE")) ctx->tp_pause_calls = (uint32_t)atoi(e);
-  if (const char* e = getenv("LB_FAULT_RERUN")) ctx->fault_rerun = atoi(e) != 0;
-  if (const char* e = getenv("LB_GT_LP")) ctx->gt_lp = atoi(e) != 0;
-  if (const char* e = getenv("LB_PRIO_KCOPY")) ctx->prio_kcopy = atoi(e) != 0;
-  if (const char* e = getenv("LB_DAG")) ctx->dag = atoi(e) != 0;
-  if (const char* e = getenv("LB_STAGE_EVENTS")) ctx->stage_events = atoi(e) != 0;
-  for (int s = 0; s < lb_ctx::kMaxSlots; s++)
-    ctx->streams_per_slot[s] = lane ? 1 : ctx->n_slots <= 2 ? 2 : (ctx->n_slots == 3 && s == 0) ? 2 : 1;
-  ctx->streams_per_slot[ctx->n_slots] = 1;  // the priority lane
-  // LB_SLOT0_STREAMS=1|2 overrides slot 0's two-stream DAG (the synchronous, lowest-latency slot)
-  if (const char* e = getenv("LB_SLOT0_STREAMS")) ctx->streams_per_slot[0] = atoi(e) == 1 ? 1 : 2;
+  ctx->ccfg = ccfg;
+  ctx->plan = plan;
+  config_from_env(ctx->cfg, env_lookup);
+  ctx->sm_mode = ccfg.sm_randomized ? LB_SM_RANDOMIZED : LB_SM_PLAIN;
   int prio_least = 0, prio_greatest = 0;
   if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) prio_greatest = 0;
-  // The priority lane's CU reservation.  A running workgroup is never
-  // preempted and a priority stream only reorders dispatch, so under load a latency-path
-  // call would wait for a whole CU to drain.  LB_PRIO_CUS=K (default 64 of 256; 0 = off):
-  // masked streams that leave the K highest-numbered CUs to the priority lane.
-  // LB_PRIO_DYN (default 1): throughput calls take them only while the priority lane has
-  // been used within the last LB_PRIO_HOLD_MS (default 250), the full streams otherwise,
-  // so a GPU without priority traffic keeps every CU.  Measured (profiles/r04/prio_ab/,
-  // legs_ab/): 1-set / 128-set p50 under 16 calls in flight 1.2x / 1.9x idle (4-6x without),
-  // C2 throughput unchanged.
-  std::vector<uint32_t> cu_mask;
-  {
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    int k = cus >= 128 ? 64 : 0;
-    if (const char* e = getenv("LB_PRIO_CUS")) k = atoi(e);
-    if (lane) k = 0;  // (the reservation belongs to the throughput context: lb_mark_priority)
-    if (k > 0 && k < cus) {
-      cu_mask.assign((size_t)(cus + 31) / 32, 0u);
-      // LB_PRIO_SPREAD=1: the K reserved CUs evenly spaced over the CU ids instead (measured
-      // worse: the mask bits do not map to CUs that way)
-      const char* sp = getenv("LB_PRIO_SPREAD");
-      const bool spread = sp && atoi(sp) == 1;
-      std::vector<char> reserved((size_t)cus, 0);
-      for (int j = 0; j < k; j++) reserved[spread ? (size_t)((int64_t)(j + 1) * cus / k - 1) : (size_t)(cus - k + j)] = 1;
-      for (int c = 0; c < cus; c++)
-        if (!reserved[c]) cu_mask[c / 32] |= 1u << (c % 32);
-      ctx->prio_cus = k;
-    }
-  }
-  if (!cu_mask.empty()) {
-    const char* dy = getenv("LB_PRIO_DYN");
-    ctx->prio_dyn = !dy || atoi(dy) != 0;
-    if (const char* h = getenv("LB_PRIO_HOLD_MS")) ctx->prio_hold_ms = atof(h);
-    // every masked stream takes a hardware queue of a pool of its own, and every queue
-    // reserves scratch (§5.1): with LB_PRIO_DYN_SLOTS=K only the first K slots get one
-    // masked stream each; while the priority lane is in use new calls go to those slots
-    // (default 2: 16 + 16 ran out of scratch, like 24 queues of one pool; with 4 masked
-    // queues the queues of a second context or process on the same GPU -- bench.py's
-    // single-stream timing context, its node leg -- slowed every later call by a third,
-    // with 2 they did not)
-    ctx->prio_dyn_slots = ctx->n_slots;
-    int v = 2;
-    if (const char* k = getenv("LB_PRIO_DYN_SLOTS")) v = atoi(k);
-    if (ctx->prio_dyn && v >= 1 && v < ctx->n_slots) ctx->prio_dyn_slots = v;
-  }
-  // Every hardware queue this context opens reserves scratch for the largest private
-  // segment it runs: price all of them, not only GPU_MAX_HW_QUEUES
-  // (VERDICT r4 #7).  HIP pools the plain streams of one priority into at most
-  // GPU_MAX_HW_QUEUES queues; a CU-masked stream gets a queue of its own.
-  {
-    int maxq = 4;
-    if (const char* e = getenv("GPU_MAX_HW_QUEUES")) maxq = atoi(e) > 0 ? atoi(e) : 4;
-    int plain = 0, masked = 0;
-    const bool one = ctx->prio_dyn && ctx->prio_dyn_slots < ctx->n_slots;
-    for (int s = 0; s < ctx->n_slots; s++) {
-      const int spp = ctx->streams_per_slot[s];
-      if (cu_mask.empty() || ctx->prio_dyn) plain += spp;
-      if (!cu_mask.empty() && s < ctx->prio_dyn_slots) masked += one ? 1 : spp;
-    }
-    const char* tp = getenv("LB_TAIL_PRIO");
-    const int high = 2 + (tp && atoi(tp) == 1 ? 1 : 0);  // priority lane, aux (lb_gt_check), tail stream
-    const int queues = (plain < maxq ? plain : maxq) + (high < maxq ? high : maxq) + masked;
-    uint32_t lane = 0;
-    const size_t per_q = scratch_per_queue(device, &lane);
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 256;
-    // the largest configuration that ran: 16 plain + 2 masked + 2 high-priority queues at
-    // 3,328 private bytes per lane; 24 + 2 plain (r03) and 16 + 16 masked + 2 (r04) queues
-    // failed with HSA_STATUS_ERROR_OUT_OF_RESOURCES
-    double budget = 20.0 * 3328 * 64 * 32 * cus;
-    if (const char* e = getenv("LB_SCRATCH_BUDGET_GB")) budget = atof(e) * 1e9;
-    if ((double)per_q * queues > budget) {
-      char msg[400];
-      snprintf(msg, sizeof msg,
-               "%d hardware queues (%d plain of GPU_MAX_HW_QUEUES=%d, %d CU-masked, %d high-priority) x %u private "
-               "bytes per lane x 64 x 32 x %d CUs = %.1f GB of scratch exceeds the %.1f GB budget (20 queues at "
-               "3,328 B/lane ran; 16 + 16 masked failed with HSA_STATUS_ERROR_OUT_OF_RESOURCES)",
-               queues, plain < maxq ? plain : maxq, maxq, masked, high < maxq ? high : maxq, lane, cus,
-               per_q * (double)queues / 1e9, budget / 1e9);
-      g_create_err = msg;
-      delete ctx;
-      return LB_ERR_RESOURCES;
-    }
-    std::lock_guard<std::mutex> g(g_q_mu);
-    const int proc = pooled_queues(g_q_plain + plain, g_q_high + high, g_q_masked + masked, maxq);
-    if (lane_ctx && proc > kProcessQueueBudget) {
-      char msg[300];
-      snprintf(msg, sizeof msg,
-               "latency-lane context refused: the process would hold %d hardware queues (%d plain, %d high-priority "
-               "streams pooled into at most GPU_MAX_HW_QUEUES=%d each, %d CU-masked), above the %d that ran",
-               proc, g_q_plain + plain, g_q_high + high, maxq, g_q_masked + masked, kProcessQueueBudget);
-      g_create_err = msg;
-      delete ctx;
-      return LB_ERR_RESOURCES;
-    }
-    g_q_plain += plain;
-    g_q_high += high;
-    g_q_masked += masked;
-    ctx->q_plain = plain;
-    ctx->q_high = high;
-    ctx->q_masked = masked;
-    ctx->hw_queues = queues;
-  }
-  for (int s = 0; ok && s <= ctx->n_slots; s++) {
+  for (int s = 0; ok && s <= plan.n_slots; s++) {
     Slot& sl = ctx->slots[s];
-    for (int i = 0; ok && i < ctx->streams_per_slot[s]; i++) {
-      if (s == ctx->n_slots) {
-        ok = hipStreamCreateWithPriority(&sl.st[i], hipStreamNonBlocking, prio_greatest) == hipSuccess;
-      } else if (!cu_mask.empty()) {
-        const bool one = ctx->prio_dyn && ctx->prio_dyn_slots < ctx->n_slots;  // one masked stream per slot
-        if (s < ctx->prio_dyn_slots && !(one && i > 0))
-          ok = hipExtStreamCreateWithCUMask(&sl.st_mask[i], (uint32_t)cu_mask.size(), cu_mask.data()) == hipSuccess;
-        else if (one && i > 0)
-          sl.st_mask[i] = sl.st_mask[0];
-        if (ok && ctx->prio_dyn) ok = hipStreamCreateWithFlags(&sl.st_full[i], hipStreamNonBlocking) == hipSuccess;
-        sl.st[i] = ctx->prio_dyn ? sl.st_full[i] : sl.st_mask[i];
-      } else {
-        ok = hipStreamCreateWithFlags(&sl.st[i], hipStreamNonBlocking) == hipSuccess;
-      }
+    for (int i = 0; i < 2; i++) {
+      const StreamPlan& e = plan.st[s][i];
+      if (e.mask == ST_ALIAS0) sl.st_mask[i] = sl.st_mask[0];
+      if (ok && e.mask == ST_OWN)
+        ok = hipExtStreamCreateWithCUMask(&sl.st_mask[i], (uint32_t)plan.cu_mask.size(), plan.cu_mask.data()) == hipSuccess;
+      if (e.full == ST_ALIAS0) sl.st_full[i] = sl.st_full[0];
+      if (ok && e.full == ST_OWN) ok = hipStreamCreateWithFlags(&sl.st_full[i], hipStreamNonBlocking) == hipSuccess;
+      if (ok && e.full == ST_HIGH)
+        ok = hipStreamCreateWithPriority(&sl.st_full[i], hipStreamNonBlocking, prio_greatest) == hipSuccess;
+      sl.st[i] = e.starts_masked() ? sl.st_mask[i] : sl.st_full[i];
     }
-    if (ctx->streams_per_slot[s] == 1) {
-      sl.st_full[1] = sl.st_full[0];
-      sl.st_mask[1] = sl.st_mask[0];
-    }
-    if (ctx->streams_per_slot[s] == 1) sl.st[1] = sl.st[0];
     for (int i = 0; ok && i < 8; i++) ok = hipEventCreateWithFlags(&sl.dep[i], hipEventDisableTiming) == hipSuccess;
     for (int i = 0; ok && i < Slot::kMaxStages; i++)
       ok = hipEventCreate(&sl.ev0[i]) == hipSuccess && hipEventCreate(&sl.ev1[i]) == hipSuccess;
@@ -1599,17 +1431,12 @@ static int create_ctx(int device, lb_ctx** out_ctx, bool lane) {
   // the host combine's one-wave final exponentiation must not queue behind the
   // calls in flight (their 1-wave/SIMD kernels fill every SIMD): highest priority
   ok = ok && hipStreamCreateWithPriority(&ctx->aux_stream, hipStreamNonBlocking, prio_greatest) == hipSuccess;
-  {
-    // off by default: one shared high-priority stream for every slot's merged check
-    // measured 2.40-2.43 vs 2.56-2.57 M sets/s (profiles/ab_r02s/r02s_d_*.json)
-    const char* e = getenv("LB_TAIL_PRIO");
-    if (e && atoi(e) == 1)
-      ok = ok && hipStreamCreateWithPriority(&ctx->tail_stream, hipStreamNonBlocking, prio_greatest) == hipSuccess;
-  }
+  if (plan.tail_stream)
+    ok = ok && hipStreamCreateWithPriority(&ctx->tail_stream, hipStreamNonBlocking, prio_greatest) == hipSuccess;
   // the latency path's round programs (2.6 MB) are uploaded here, before any call is in
   // flight: a synchronous copy on the first latency-path call would wait for the
   // throughput calls already running on blocking (CU-masked) streams
-  if (ok && (ctx->cfg.lp_max_sets || ctx->cfg.mtail_lp || ctx->gt_lp || ctx->cfg.rtail_lp) && lp_ensure(ctx) != LB_OK)
+  if (ok && (ctx->cfg.lp_max_sets || ctx->cfg.mtail_lp || ctx->ccfg.gt_lp || ctx->cfg.rtail_lp) && lp_ensure(ctx) != LB_OK)
     ok = false;
   // the priority slot's staging and workspace sized here for a latency-path call of
   // lp_max_sets sets (16 keys each by bytes): growing them later frees the old buffers,
@@ -1617,7 +1444,7 @@ static int create_ctx(int device, lb_ctx** out_ctx, bool lane) {
   // throughput call in flight (the node leg's first 128-set priority job under load took
   // 0.9-1.5 s, profiles/r05/node_q/)
   if (ok && ctx->cfg.lp_max_sets) {
-    Slot& pl = ctx->slots[ctx->n_slots];
+    Slot& pl = ctx->slots[ctx->plan.n_slots];
     const size_t ns = ctx->cfg.lp_max_sets;  // (16 keys a set, uncompressed signatures, every set a request)
     const HostCallShape shape{ns, ns, 16 * ns, 192 * ns, 0, true, false};
     const size_t io = layout_host_call(shape).end;
@@ -1647,13 +1474,16 @@ int lb_mark_priority(lb_ctx* ctx) {
 int lb_destroy(lb_ctx* ctx) {
   if (!ctx) return LB_OK;
   (void)hipSetDevice(ctx->device);
-  for (int s = 0; s <= ctx->n_slots; s++) {
+  for (int s = 0; s <= ctx->plan.n_slots; s++) {
     Slot& sl = ctx->slots[s];
-    for (int i = 0; i < ctx->streams_per_slot[s]; i++) {
-      if (sl.st[i]) (void)hipStreamSynchronize(sl.st[i]);
-      if (sl.st_full[i]) (void)hipStreamSynchronize(sl.st_full[i]);
-      if (sl.st_mask[i]) (void)hipStreamSynchronize(sl.st_mask[i]);
+    // the streams the plan made this slot's own (a failed creation left the later ones null)
+    hipStream_t own[4];
+    int n_own = 0;
+    for (int i = 0; i < 2; i++) {
+      if (owned(ctx->plan.st[s][i].full) && sl.st_full[i]) own[n_own++] = sl.st_full[i];
+      if (owned(ctx->plan.st[s][i].mask) && sl.st_mask[i]) own[n_own++] = sl.st_mask[i];
     }
+    for (int i = 0; i < n_own; i++) (void)hipStreamSynchronize(own[i]);
     if (sl.d_ws) (void)hipFree(sl.d_ws);
     if (sl.h_pin) (void)hipHostFree(sl.h_pin);
     for (int i = 0; i < 8; i++)
@@ -1669,14 +1499,7 @@ int lb_destroy(lb_ctx* ctx) {
     if (sl.h_stats) (void)hipHostFree(sl.h_stats);
     if (sl.h_partial) (void)hipHostFree(sl.h_partial);
     if (sl.h_clk) (void)hipHostFree(sl.h_clk);
-    for (int i = 0; i < ctx->streams_per_slot[s]; i++) {
-      if (sl.st_mask[i] || sl.st_full[i]) {  // (st[] is one of these pairs)
-        if (sl.st_mask[i] && !(i > 0 && sl.st_mask[i] == sl.st_mask[0])) (void)hipStreamDestroy(sl.st_mask[i]);
-        if (sl.st_full[i]) (void)hipStreamDestroy(sl.st_full[i]);
-      } else if (sl.st[i]) {
-        (void)hipStreamDestroy(sl.st[i]);
-      }
-    }
+    for (int i = 0; i < n_own; i++) (void)hipStreamDestroy(own[i]);
   }
   if (ctx->d_table) (void)hipFree(ctx->d_table);
   if (ctx->aux_stream) {
@@ -1700,9 +1523,9 @@ int lb_destroy(lb_ctx* ctx) {
     if (e) (void)hipEventDestroy(e);
   {
     std::lock_guard<std::mutex> g(g_q_mu);
-    g_q_plain -= ctx->q_plain;
-    g_q_high -= ctx->q_high;
-    g_q_masked -= ctx->q_masked;
+    g_q.plain -= ctx->plan.q_plain;
+    g_q.high -= ctx->plan.q_high;
+    g_q.masked -= ctx->plan.q_masked;
   }
   delete ctx;
   return LB_OK;
@@ -1720,12 +1543,14 @@ int lb_scratch_per_queue(int device, uint64_t* out_bytes, uint32_t* out_lane_byt
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0 || device < 0 || device >= n) return LB_ERR_NO_DEVICE;
   if (!out_bytes) return LB_ERR_INVALID_ARGUMENT;
   if (hipSetDevice(device) != hipSuccess) return LB_ERR_DEVICE;
-  *out_bytes = scratch_per_queue(device, out_lane_bytes);
+  DeviceFacts dev;
+  *out_bytes = scratch_per_queue(device, &dev);
+  if (out_lane_bytes) *out_lane_bytes = dev.lane_bytes;
   return LB_OK;
 }
 
-int lb_slots(const lb_ctx* ctx) { return ctx ? ctx->n_slots : 0; }
-int lb_hw_queues(const lb_ctx* ctx) { return ctx ? ctx->hw_queues : 0; }
+int lb_slots(const lb_ctx* ctx) { return ctx ? ctx->plan.n_slots : 0; }
+int lb_hw_queues(const lb_ctx* ctx) { return ctx ? ctx->plan.hw_queues : 0; }
 int lb_last_call_streams(const lb_ctx* ctx) { return ctx ? ctx->last_call_streams : 0; }
 int lb_last_latency_clocks(const lb_ctx* ctx, uint64_t* out4) {
   if (!ctx || !out4) return LB_ERR_INVALID_ARGUMENT;
@@ -1757,7 +1582,7 @@ int lb_last_stage_times(const lb_ctx* ctx, float* out_ms, const char** out_names
 static bool prio_active(lb_ctx* ctx) {
   const int64_t now = std::chrono::duration_cast<std::chrono::nanoseconds>(
                           std::chrono::steady_clock::now().time_since_epoch()).count();
-  return ctx->prio_dyn && (double)(now - ctx->last_prio_ns.load(std::memory_order_relaxed)) < ctx->prio_hold_ms * 1e6;
+  return ctx->plan.prio_dyn && (double)(now - ctx->last_prio_ns.load(std::memory_order_relaxed)) < ctx->plan.prio_hold_ms * 1e6;
 }
 
 // A call about to run on slot sl (idle: finish_slot has retired its last call): with
@@ -1770,11 +1595,9 @@ static void pick_streams(lb_ctx* ctx, Slot& sl) {
                             std::memory_order_relaxed);
     return;
   }
-  if (!ctx->prio_dyn) return;
+  if (!ctx->plan.prio_dyn) return;
   if (prio_active(ctx)) {
-    // a slot without masked streams queues on those of slot (s mod K) -- on the GPU, not
-    // in finish_slot: the submitting thread never waits longer than the round robin makes it
-    const Slot& m = sl.st_mask[0] ? sl : ctx->slots[(&sl - ctx->slots) % ctx->prio_dyn_slots];
+    const Slot& m = ctx->slots[ctx->plan.mask_slot[&sl - ctx->slots]];
     sl.st[0] = m.st_mask[0];
     sl.st[1] = m.st_mask[1];
   } else {
@@ -1989,14 +1812,14 @@ static void fill_stats(lb_ctx* ctx, uint64_t ticket, lb_verify_stats* stats) {
 // every slot holds a pending partial is the next one taken anyway.
 static Slot& next_async_slot(lb_ctx* ctx) {  // internal: not part of the C ABI
   int s = ctx->next_slot;
-  for (int k = 0; k < ctx->n_slots; k++) {
-    const int c = (ctx->next_slot + k) % ctx->n_slots;
+  for (int k = 0; k < ctx->plan.n_slots; k++) {
+    const int c = (ctx->next_slot + k) % ctx->plan.n_slots;
     if (!ctx->slots[c].partial_pending) {
       s = c;
       break;
     }
   }
-  ctx->next_slot = (s + 1) % ctx->n_slots;
+  ctx->next_slot = (s + 1) % ctx->plan.n_slots;
   return ctx->slots[s];
 }
 
@@ -2115,9 +1938,9 @@ int lb_verify_requests_finish(lb_ctx* ctx, uint64_t ticket, int merged_ok) {
     // (a failure from here on leaves the outputs provisional: the record says so, and
     // lb_wait returns the error instead of them)
     r->failed = true;
-    ctx->tp_pause = ctx->tp_pause_calls;  // (the next two-phase calls: legacy mode)
+    ctx->tp_pause = ctx->ccfg.tp_pause;  // (the next two-phase calls: legacy mode)
     if (Slot* sl = slot_of_ticket(ctx, ticket)) LB_TRY(finish_slot(ctx, *sl));
-    if (ctx->fault_rerun) {  // (fault injection for the tests: the re-run's submission fails)
+    if (ctx->ccfg.fault_rerun) {  // (fault injection for the tests: the re-run's submission fails)
       ctx->err = "LB_FAULT_RERUN: the failed combine's re-verification was not submitted";
       return LB_ERR_DEVICE;
     }
@@ -2147,7 +1970,7 @@ int lb_verify_requests_finish(lb_ctx* ctx, uint64_t ticket, int merged_ok) {
     ctx->err = "ticket is not a two-phase call";
     return LB_ERR_INVALID_ARGUMENT;
   }
-  if (!merged_ok && ctx->cfg.tp_release_cfg) ctx->tp_pause = ctx->tp_pause_calls;  // (failures go on: stay legacy)
+  if (!merged_ok && ctx->cfg.tp_release_cfg) ctx->tp_pause = ctx->ccfg.tp_pause;  // (failures go on: stay legacy)
   return finish_partial(ctx, *sl, merged_ok != 0);
 }
 
@@ -2156,7 +1979,7 @@ int lb_gt_check(lb_ctx* ctx, uint32_t n, const uint8_t* partials576, int32_t* ou
   LB_HIP(hipSetDevice(ctx->device));
   // (+ the combined product's 12 records for the round-program final exponentiation)
   const size_t need = (((size_t)n * LB_GT_BYTES + 255) & ~(size_t)255) + 256 + 12 * 64;
-  if (ctx->gt_lp) LB_TRY(lp_ensure(ctx));
+  if (ctx->ccfg.gt_lp) LB_TRY(lp_ensure(ctx));
   if (need > ctx->aux_cap) {
     LB_HIP(hipStreamSynchronize(ctx->aux_stream));
     if (ctx->d_aux) LB_HIP(hipFree(ctx->d_aux));
@@ -2177,7 +2000,7 @@ int lb_gt_check(lb_ctx* ctx, uint32_t n, const uint8_t* partials576, int32_t* ou
     memcpy(ctx->h_aux + 256, partials576, (size_t)n * LB_GT_BYTES);
     LB_HIP(hipMemcpyAsync(d_in, ctx->h_aux + 256, (size_t)n * LB_GT_BYTES, hipMemcpyHostToDevice, ctx->aux_stream));
   }
-  if (ctx->gt_lp) {
+  if (ctx->ccfg.gt_lp) {
     // the product (one wave), then the final exponentiation as a round program on one
     // workgroup (~420 rounds) instead of the one-wave chain
     uint32_t* d_rec = reinterpret_cast<uint32_t*>(ctx->d_aux + 256 + (((size_t)n * LB_GT_BYTES + 255) & ~(size_t)255));
@@ -2672,7 +2495,7 @@ int sm_prepare(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, bool agg, 
       const uint32_t j = b->pubkey_indices[i];
       if ((j & LB_PK_ROW_FLAG) && (size_t)(j & LB_PK_ROW_MASK) + 1 > n_rows) n_rows = (j & LB_PK_ROW_MASK) + 1;
     }
-  s = SmShape{nj, ns, b->sig_offsets[ns], n_rows, by_index, agg, ns && ns <= LB_SM_DEC_MAX && ctx->sm_lp_decode, front_only,
+  s = SmShape{nj, ns, b->sig_offsets[ns], n_rows, by_index, agg, ns && ns <= LB_SM_DEC_MAX && ctx->ccfg.sm_lp_decode, front_only,
               front_only ? 0 : pipeline_ws_bytes(ctx, nj, nj), front_only ? 0 : pipeline_ws_bytes(ctx, ns, ns)};
   L = layout_same_message(s, ns);
   LB_TRY(ensure_pin(ctx, sl, L.pin_end));
@@ -2952,7 +2775,7 @@ int sm_advance_launch(lb_ctx* ctx, Slot& sl, bool block) {
 // Launch the phase 2 of every same-message call whose phase 1 has completed
 // (called from every async entry point and lb_wait: no blocking).
 int sm_pump(lb_ctx* ctx) {
-  for (int s = 0; s <= ctx->n_slots; s++) {
+  for (int s = 0; s <= ctx->plan.n_slots; s++) {
     Slot& sl = ctx->slots[s];
     // (another call's failure is not this caller's: it stays on that slot's ticket)
     if (sl.busy && sl.sm.active && sl.sm.phase == 1) (void)sm_advance(ctx, sl, false);
@@ -3468,7 +3291,7 @@ int kzg_tail(lb_ctx* ctx, const KzgBufs& b, uint32_t n, uint32_t mode) {
 // stage times of a KZG call: names[i] spans ev[first + i] .. ev[first + i + 1]
 int kzg_publish_times(lb_ctx* ctx, int first, int count, const char* const* names) {
   ctx->n_stages = 0;
-  if (!ctx->stage_events) return LB_OK;
+  if (!ctx->ccfg.stage_events) return LB_OK;
   for (int i = 0; i < count; i++) {
     float ms = 0.f;
     LB_HIP(hipEventElapsedTime(&ms, ctx->kzg.ev[first + i], ctx->kzg.ev[first + i + 1]));

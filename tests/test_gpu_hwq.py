@@ -101,3 +101,89 @@ d.close()
     print("\n", out)
     assert out["valid"] == [1, 1, 1], out
     assert out["streams"] == 2, out
+
+
+# A context as plan_context (csrc/bls_ctx_plan.h) lays it out, created and used: rows of the table
+# in tests/test_ctx_plan.py.  The refused configurations are checked there, on the CPU only.
+CALLS = r"""
+import json, sys, os
+sys.path.insert(0, %r)
+import numpy as np
+from lodestar_amd import native
+from oracle import bls12_381 as O
+import hashlib
+d = native.Device(0)
+out = {"slots": d.slots(), "hw_queues": d.hw_queues()}
+d.set_latency_path(0)
+sks = [O.interop_secret_key(i) for i in range(8)]
+sk_be = [s.to_bytes(32, "big") for s in sks]
+msgs = [hashlib.sha256(bytes([i])).digest() for i in range(8)]
+pks = d.sk_to_pk(sk_be)
+sigs = d.sign(sk_be, msgs)
+blob, offs = native.pack_blobs(sigs)
+# a latency-path call: the priority lane in use (LB_PRIO_DYN: the next calls take the masked streams)
+d.set_latency_path(1024)
+r0 = d.verify_requests(np.array([0, 1], np.uint32), np.frombuffer(b"".join(pks[:1]), np.uint8), None,
+                       np.frombuffer(b"".join(msgs[:1]), np.uint8), blob[:96], offs[:2], bytes(32))
+d.set_latency_path(0)
+r = d.verify_requests(np.array([0, 4, 8], np.uint32), np.frombuffer(b"".join(pks), np.uint8), None,
+                      np.frombuffer(b"".join(msgs), np.uint8), blob, offs, bytes(32))
+out["valid"] = [int(r0.valid[0])] + [int(v) for v in r.valid]
+out["streams"] = d.last_call_streams()
+d.close()
+print(json.dumps(out))
+""" % ROOT
+
+_CTX_SWITCHES = ("LB_SLOTS", "LB_SLOT0_STREAMS", "LB_PRIO_DYN_SLOTS", "LB_PRIO_CUS", "LB_PRIO_DYN", "LB_PRIO_SPREAD",
+                 "LB_TAIL_PRIO", "LB_SCRATCH_BUDGET_GB", "LB_DAG")
+
+
+def _run(code, queues, **env_extra):
+    env = dict(os.environ, GPU_MAX_HW_QUEUES=str(queues))
+    for k in _CTX_SWITCHES:
+        env.pop(k, None)
+    env.update(env_extra)
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+@pytest.mark.parametrize("env, slots, queues", [
+    ({}, 4, 8),                                        # four single-stream slots, two of them with a masked stream
+    ({"LB_SLOTS": "2"}, 2, 10),                        # two two-stream slots, full and masked pairs
+    ({"LB_SLOTS": "2", "LB_PRIO_DYN": "0"}, 2, 6),     # masked pairs only
+    ({"LB_PRIO_CUS": "0"}, 4, 6),                      # no reservation: plain streams only
+], ids=["default", "slots2", "slots2_static_mask", "no_mask"])
+def test_planned_context_runs(env, slots, queues):
+    out = _run(CALLS, 4, **env)
+    print("\n", env, out)
+    assert (out["slots"], out["hw_queues"]) == (slots, queues), out
+    assert out["valid"] == [1, 1, 1], out
+    assert out["streams"] == 2, out
+
+
+LANE = r"""
+import ctypes, json, sys
+sys.path.insert(0, %r)
+from lodestar_amd import native
+lib = native.load_library()
+out = {"lane_queues": [], "lane_rc": [], "main_queues": []}
+for _ in range(2):  # (the second round is priced on a tally the first has left)
+    d = native.Device(0)
+    out["main_queues"].append(d.hw_queues())
+    h = ctypes.c_void_p()
+    out["lane_rc"].append(lib.lb_create_lane(0, ctypes.byref(h)))
+    out["lane_queues"].append(lib.lb_hw_queues(h) if h else 0)
+    if h:
+        lib.lb_destroy(h)
+    d.close()
+print(json.dumps(out))
+""" % ROOT
+
+
+def test_lane_context_and_tally_release():
+    """The default context and a latency-lane context are the 22 queues a process may hold; a tally
+    not released by lb_destroy would refuse the second round's lane context (tests/test_ctx_plan.py)."""
+    out = _run(LANE, 16)
+    print("\n", out)
+    assert out == {"main_queues": [20, 20], "lane_rc": [0, 0], "lane_queues": [3, 3]}, out
