@@ -485,6 +485,89 @@ int lb_pubkey_table_truncate(lb_ctx* ctx, uint32_t n);
 int lb_aggregate_pubkeys_indexed(lb_ctx* ctx, uint32_t n, const uint32_t* indices, uint8_t* out96,
                                  uint8_t* out_status);
 
+/* ---- device-resident index lists: committees from bits ----------------------
+ * Mirror of an epoch's EpochShuffling.shuffling (state-transition/src/util/epochShuffling.ts:62-101)
+ * and of the sync committee's validator indices, one step above the pubkey table in the
+ * reference's data flow: an aggregate set then says "this slice of that list, these bits"
+ * (the attestation as it arrived) instead of one validator index per participant, and the
+ * walk aggregationBits.intersectValues(getBeaconCommittee(slot, index))
+ * (state-transition/src/cache/epochCache.ts:684-685) runs on the GPU in front of the pipeline.
+ *
+ * A context holds LB_INDEX_LISTS lists of uint32_t validator indices in HBM (previous, current
+ * and next shuffling, two sync committees, spares: the next epoch loads into a free id while
+ * the current one serves calls).  A lb_create_lane context has lists of its own, as it has a
+ * pubkey table of its own: load the same lists into both.
+ * lb_index_list_put and lb_index_list_shuffle wait for the context's calls in flight, like
+ * lb_pubkey_table_append (a call's expansion reads the list on its stream).  A list id
+ * >= LB_INDEX_LISTS, or a read beyond the list, -> LB_ERR_INVALID_ARGUMENT, nothing changed. */
+#define LB_INDEX_LISTS 8
+#define LB_SHUFFLE_ROUNDS 90
+#define LB_SHUFFLE_MAX 4194304u
+/* Store indices[0..n) as list `list`, as given (a sync committee's 512 indices, duplicates
+ * allowed).  n == 0 empties the id. */
+int lb_index_list_put(lb_ctx* ctx, uint32_t list, uint32_t n, const uint32_t* indices);
+/* Store unshuffleList(active_indices, seed) (state-transition/src/util/shuffle.ts, the spec's
+ * LB_SHUFFLE_ROUNDS rounds): out[i] = active_indices[compute_shuffled_index(i, n, seed)], the
+ * array computeEpochShuffling slices its committees from.  out_shuffling (optional, n): the
+ * stored list copied back, so the host needs no unshuffleList of its own.  n <= 1 stores the
+ * input unchanged; n > LB_SHUFFLE_MAX -> LB_ERR_INVALID_ARGUMENT.  lb_last_stage_times
+ * then reports one stage, shuffle (the round sources and the per-position rounds). */
+int lb_index_list_shuffle(lb_ctx* ctx, uint32_t list, uint32_t n, const uint32_t* active_indices,
+                          const uint8_t* seed32, uint32_t* out_shuffling);
+/* Entries of list `list` (0 for an id never loaded). */
+int lb_index_list_size(const lb_ctx* ctx, uint32_t list, uint32_t* out_n);
+/* Entries [first, first + n) of the list. */
+int lb_index_list_read(lb_ctx* ctx, uint32_t list, uint32_t first, uint32_t n, uint32_t* out);
+
+/* A set's keys by descriptor, one entry per set of a lb_request_batch whose pubkeys,
+ * pk_offsets and pubkey_indices are all NULL.  Set i's keys are the validator indices the
+ * entry lists, in list order, into the device pubkey table; the call is then exactly the
+ * lb_verify_requests* call with those pubkey_indices (an expansion kernel writes them in
+ * front of the unchanged pipeline: expand_keys in lb_last_stage_times):
+ *   - zero keys (a BITS set with no bit set, a SLICE with len == 0) -> LB_REQ_EMPTY_AGGREGATE;
+ *   - an index >= the table size -> LB_REQ_BAD_PUBKEY;
+ *   - bits at positions >= len in the last byte are ignored;
+ *   - an unloaded (empty) or unknown list, a + len beyond the list or the pool,
+ *     bits_off + ceil(len / 8) beyond n_bits_bytes, an unknown kind -> LB_ERR_INVALID_ARGUMENT
+ *     at submit, nothing enqueued.
+ * The host checks these bounds and counts each set's keys; the device trusts no count of
+ * its own.  Outputs, tickets, lb_wait / lb_poll / lb_partial_* / lb_verify_requests_finish,
+ * routing by size and stats are those of the lb_verify_requests* namesakes.  Wherever those
+ * ask that inputs stay valid until lb_wait returns (the async forms' buffers; the released
+ * two-phase flow, which re-verifies from the caller's buffers), that covers the lb_key_source
+ * struct and the three arrays it points to as well. */
+#define LB_KEYS_DIRECT 0u /* a = the validator index: a one-key set                            */
+#define LB_KEYS_SLICE 1u  /* keys = key_pool[a .. a+len): explicit indices (IndexedAttestation) */
+#define LB_KEYS_BITS 2u   /* keys = list[a + j] for every set bit j < len of bits[bits_off ..)  */
+typedef struct {
+  uint32_t kind, list, a, len, bits_off;
+} lb_set_keys;
+typedef struct {
+  const lb_set_keys* sets; /* batch->n_sets */
+  const uint32_t* key_pool;
+  uint32_t n_pool;
+  const uint8_t* bits;
+  uint32_t n_bits_bytes; /* bit j of a set = (bits[bits_off + j/8] >> (j%8)) & 1 */
+} lb_key_source;
+int lb_verify_requests_keys(lb_ctx* ctx, const lb_request_batch* batch, const lb_key_source* keys,
+                            uint8_t* out_request_valid, uint8_t* out_request_error, uint8_t* out_set_status,
+                            lb_verify_stats* stats);
+int lb_verify_requests_keys_async(lb_ctx* ctx, const lb_request_batch* batch, const lb_key_source* keys,
+                                  uint8_t* out_request_valid, uint8_t* out_request_error, uint8_t* out_set_status,
+                                  uint64_t* out_ticket);
+int lb_verify_requests_keys_priority_async(lb_ctx* ctx, const lb_request_batch* batch, const lb_key_source* keys,
+                                           uint8_t* out_request_valid, uint8_t* out_request_error,
+                                           uint8_t* out_set_status, uint64_t* out_ticket);
+/* The two-phase form (host buffers only: no LB_BATCH_DEVICE). */
+int lb_verify_requests_keys_partial_async(lb_ctx* ctx, const lb_request_batch* batch, const lb_key_source* keys,
+                                          uint8_t* out_request_valid, uint8_t* out_request_error,
+                                          uint8_t* out_set_status, uint64_t* out_ticket);
+/* Stage-level entry (tests): the expansion alone.  out_pk_offsets: n_sets + 1;
+ * out_indices: pk_offsets[n_sets] of them, at most max_indices (more ->
+ * LB_ERR_INVALID_ARGUMENT, nothing written). */
+int lb_expand_set_keys(lb_ctx* ctx, uint32_t n_sets, const lb_key_source* keys, uint32_t* out_pk_offsets,
+                       uint32_t* out_indices, uint32_t max_indices);
+
 /* ---- signing roots (the step before the verifier) --------
  * computeSigningRoot(type, obj, domain) = hash_tree_root(SigningData{hash_tree_root(obj), domain})
  * (state-transition/src/util/signingRoot.ts:7-13), SSZ merkleization on the GPU.

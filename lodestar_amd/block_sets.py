@@ -37,7 +37,7 @@ import struct
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
-from .verifier import PublicKey, SignatureSet, SignatureSetType
+from .verifier import PublicKey, SignatureSet, SignatureSetType, bits_set
 
 SLOTS_PER_EPOCH = 32
 DOMAIN_BEACON_PROPOSER = bytes([0, 0, 0, 0])
@@ -438,14 +438,26 @@ class BlockSignatureSetBuilder:
     roots: the GPU (lodestar_amd.native.Device) or any object with its
     signing_roots_attestation / signing_roots_chunks methods.
     committee(slot, index) -> validator indices of that beacon committee;
-    sync_committee(slot) -> the 512 validator indices of the sync committee (altair)."""
+    sync_committee(slot) -> the 512 validator indices of the sync committee (altair).
 
-    def __init__(self, roots, config: ChainConfig, committee: Callable[[int, int], Sequence[int]],
-                 sync_committee: Optional[Callable[[int], Sequence[int]]] = None):
+    With the epoch's shuffling and the sync committee resident on the GPU (index lists,
+    DeviceBackend.sync_shuffling / put_index_list) the walk over committee and bits moves there:
+    committee_slices(slot, index) -> (list_id, start, length), the committee as a slice of an
+    index list, makes every attestation a bits set (verifier.bits_set) straight from its SSZ
+    bitlist, delimiter bit stripped, and `committee` is not called; sync_committee_list, the id
+    of the list holding the sync committee, does the same for the sync aggregate's bitvector.
+    Attester slashings keep their explicit indices.  Without them, sets are as before."""
+
+    def __init__(self, roots, config: ChainConfig, committee: Optional[Callable[[int, int], Sequence[int]]],
+                 sync_committee: Optional[Callable[[int], Sequence[int]]] = None,
+                 committee_slices: Optional[Callable[[int, int], Tuple[int, int, int]]] = None,
+                 sync_committee_list: Optional[int] = None):
         self.roots = roots
         self.config = config
         self.committee = committee
         self.sync_committee = sync_committee
+        self.committee_slices = committee_slices
+        self.sync_committee_list = sync_committee_list
 
     def build(self, signed_blocks: Sequence[bytes], skip_proposer_signature: bool = False) -> List[List[SignatureSet]]:
         blocks = []
@@ -491,6 +503,16 @@ class BlockSignatureSetBuilder:
             # indexedAttestation.ts:40-48 with epochCtx.getIndexedAttestation: committee members whose bit is set
             for a in b.attestations:
                 aslot, aindex = struct.unpack_from("<QQ", a.data, 0)
+                if self.committee_slices is not None:
+                    lid, start, length = self.committee_slices(aslot, aindex)
+                    last = a.aggregation_bits[-1] if a.aggregation_bits else 0
+                    if not last or (len(a.aggregation_bits) - 1) * 8 + last.bit_length() - 1 != length:
+                        raise SszError("aggregation_bits length != committee size")
+                    raw = bytearray(a.aggregation_bits)
+                    raw[-1] &= ~(1 << (last.bit_length() - 1)) & 0xFF  # the delimiter bit
+                    p.append((att(a.data, st), ("bits", lid, start, length, bytes(raw[:(length + 7) // 8])),
+                              a.signature))
+                    continue
                 members = list(self.committee(aslot, aindex))
                 bits = _bitlist_bits(a.aggregation_bits)
                 nbits = (len(a.aggregation_bits) - 1) * 8 + a.aggregation_bits[-1].bit_length() - 1
@@ -508,10 +530,14 @@ class BlockSignatureSetBuilder:
                           [b.proposer_index], b.signature))
             # processSyncCommittee.ts:88-111: participants sign the parent root at the previous slot
             if fork_seq(b.fork) >= fork_seq("altair") and b.sync_bits is not None:
-                if self.sync_committee is None:
+                if self.sync_committee_list is not None:
+                    part = ("bits", self.sync_committee_list, 0, SYNC_COMMITTEE_SIZE, bytes(b.sync_bits)) \
+                        if any(b.sync_bits) else []
+                elif self.sync_committee is None:
                     raise ValueError("altair+ blocks need sync_committee(slot)")
-                members = list(self.sync_committee(b.slot))
-                part = [members[i] for i in range(SYNC_COMMITTEE_SIZE) if (b.sync_bits[i // 8] >> (i % 8)) & 1]
+                else:
+                    members = list(self.sync_committee(b.slot))
+                    part = [members[i] for i in range(SYNC_COMMITTEE_SIZE) if (b.sync_bits[i // 8] >> (i % 8)) & 1]
                 if part:
                     prev = max(b.slot, 1) - 1
                     p.append((chunk([b.parent_root], cfg.domain(DOMAIN_SYNC_COMMITTEE, st, prev)), part,
@@ -544,6 +570,9 @@ class BlockSignatureSetBuilder:
             sets = []
             for ref, idx, sig in p:
                 root = roots_c[ref[1]][ref[2]] if ref[0] == "c" else roots_a[ref[1]]
+                if isinstance(idx, tuple) and idx[0] == "bits":  # a committee slice and its bits
+                    sets.append(bits_set(idx[1], idx[2], idx[3], idx[4], root, bytes(sig)))
+                    continue
                 if isinstance(idx, tuple):  # a BLS change: its own pubkey, no validator index
                     sets.append(SignatureSet(SignatureSetType.single, root, bytes(sig),
                                              pubkey=PublicKey(uncompressed=keys96[idx[1]])))

@@ -152,6 +152,39 @@ inline HostCallLayout layout_host_call(const HostCallShape& s) {
   return L;
 }
 
+// A host-buffer call whose sets name their keys by descriptor (lb_verify_requests_keys*): behind
+// the host call's own list (from its `end`; that call is laid out with pk_off and by_index and
+// no key of its own, n_pk == 0) come the key source's three arrays, staged like the inputs, and
+// the indices the expansion writes, n_keys of them -- the pubkey_indices the pipeline then
+// reads.  The pinned staging holds [0, in_end); the pipeline's workspace begins at `end`.
+struct KeyShape {
+  size_t n_sets = 0, n_pool = 0, n_bits_bytes = 0;
+  size_t n_keys = 0;  // what the sets expand to in all (the host's count)
+};
+enum KeyBuf : int { KB_SETS, KB_POOL, KB_BITS, KB_IDX, KB_COUNT };
+static constexpr int KB_INPUTS = KB_IDX;  // [KB_SETS, KB_INPUTS): staged from the caller's arrays
+static constexpr size_t SZ_SET_KEYS = 20;  // sizeof(lb_set_keys)
+struct KeyLayout {
+  size_t off[KB_COUNT], size[KB_COUNT];
+  size_t in_end;  // the staged part ends here (a multiple of kCarveAlign)
+  size_t end;
+};
+inline KeyLayout layout_key_source(const KeyShape& s, size_t from) {
+  KeyLayout L;
+  size_t at = from;
+  const auto take = [&](KeyBuf b, size_t bytes) {
+    L.off[b] = carve_take(at, bytes);
+    L.size[b] = bytes;
+  };
+  take(KB_SETS, s.n_sets * SZ_SET_KEYS);
+  take(KB_POOL, s.n_pool * 4);
+  take(KB_BITS, s.n_bits_bytes);
+  L.in_end = at = carve_align(at);
+  take(KB_IDX, s.n_keys * 4);
+  L.end = at;
+  return L;
+}
+
 // A same-message package (sm_front, sm_submit, sm_advance_launch; lb_same_message_aggregates
 // runs the front alone).  The slab, in order: the inputs; what the front leaves (decoded
 // signatures, the jobs' aggregated sets); phase 1's verdicts and an _agg call's buffers; the

@@ -209,6 +209,9 @@ struct TwoPhaseRec {
   bool device = false, finished = false, have_partial = false, failed = false, waited = false;
   uint64_t rerun = 0;  // the one-phase re-run's ticket (failed combine)
   lb_request_batch batch{};
+  // (a lb_verify_requests_keys_partial_async call: its key source, for the same re-run)
+  bool by_keys = false;
+  lb_key_source keys{};
   uint8_t *valid = nullptr, *err = nullptr, *sst = nullptr;
   uint8_t partial[LB_GT_BYTES];
 };
@@ -278,6 +281,13 @@ struct lb_ctx {
   // device-resident pubkey table (index2pubkey mirror, lb_pubkey_table_*)
   g1a* d_table = nullptr;
   uint32_t table_n = 0, table_cap = 0;
+  // device-resident index lists (lb_index_list_*): shufflings and sync committees that the sets
+  // of a lb_verify_requests_keys* call name their keys from (k_lists.hip)
+  struct IndexList {
+    uint32_t* d = nullptr;
+    uint32_t n = 0, cap = 0;
+  } lists[LB_INDEX_LISTS];
+  hipEvent_t list_ev[2] = {};  // lb_index_list_shuffle's stage time
   // timing of the last completed verify call
   int n_stages = 0;
   float stage_ms[Slot::kMaxStages] = {};
@@ -1108,6 +1118,23 @@ int validate_batch(lb_ctx* ctx, const lb_request_batch* b) {
   return LB_OK;
 }
 
+// A keys call's batch (lb_verify_requests_keys*): the sets' keys come from `ks` alone
+int validate_keys_batch(lb_ctx* ctx, const lb_request_batch* b, const lb_key_source* ks) {
+  if (!b || !ks || !b->request_offsets || !b->messages || !b->signatures || !b->sig_offsets || !b->seed ||
+      (b->n_sets && !ks->sets) || (ks->n_pool && !ks->key_pool) || (ks->n_bits_bytes && !ks->bits)) {
+    ctx->err = "null pointer in lb_request_batch / lb_key_source";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  if (b->pubkeys || b->pk_offsets || b->pubkey_indices) {
+    ctx->err = "a keys call's batch has pubkeys, pk_offsets and pubkey_indices NULL";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  return LB_OK;
+}
+int validate_host_batch(lb_ctx* ctx, const lb_request_batch* b, const lb_key_source* ks) {
+  return ks ? validate_keys_batch(ctx, b, ks) : validate_batch(ctx, b);
+}
+
 // A host <-> device copy of a call on slot sl: on the priority slot a kernel (k_copy_bytes,
 // LB_PRIO_KCOPY=0: hipMemcpyAsync), never queued on an SDMA engine behind the throughput
 // calls' staging; elsewhere hipMemcpyAsync.  Host buffers are pinned (hipHostMalloc).
@@ -1502,6 +1529,10 @@ int lb_destroy(lb_ctx* ctx) {
     for (int i = 0; i < n_own; i++) (void)hipStreamDestroy(own[i]);
   }
   if (ctx->d_table) (void)hipFree(ctx->d_table);
+  for (lb_ctx::IndexList& l : ctx->lists)
+    if (l.d) (void)hipFree(l.d);
+  for (hipEvent_t e : ctx->list_ev)
+    if (e) (void)hipEventDestroy(e);
   if (ctx->aux_stream) {
     (void)hipStreamSynchronize(ctx->aux_stream);
     (void)hipStreamDestroy(ctx->aux_stream);
@@ -1610,8 +1641,8 @@ static void pick_streams(lb_ctx* ctx, Slot& sl) {
 }
 
 // a two-phase call's record (LB_TP_RELEASE; the legacy mode keeps only the ticket ring)
-static void tp_record(lb_ctx* ctx, uint64_t ticket, const lb_request_batch* b, bool device, uint8_t* valid,
-                      uint8_t* err, uint8_t* sst) {
+static void tp_record(lb_ctx* ctx, uint64_t ticket, const lb_request_batch* b, const lb_key_source* ks, bool device,
+                      uint8_t* valid, uint8_t* err, uint8_t* sst) {
   if (!ctx->cfg.tp_release) return;
   // (the ticket ring too: a finish of a ticket whose record was reused -- finished or waited
   // for by then, tp_reusable -- is a no-op, not an error)
@@ -1623,6 +1654,8 @@ static void tp_record(lb_ctx* ctx, uint64_t ticket, const lb_request_batch* b, b
   r.finished = r.have_partial = r.failed = r.waited = false;
   r.rerun = 0;
   r.batch = *b;
+  r.by_keys = ks != nullptr;
+  r.keys = ks ? *ks : lb_key_source{};
   r.valid = valid;
   r.err = err;
   r.sst = sst;
@@ -1668,7 +1701,7 @@ static int submit_device(lb_ctx* ctx, Slot& sl, const lb_request_batch* b, uint8
   }
   LB_TRY(end_call_async(ctx, sl));
   *out_ticket = sl.ticket;
-  if (partial) tp_record(ctx, sl.ticket, b, true, d_valid, d_req_err, d_set_status);
+  if (partial) tp_record(ctx, sl.ticket, b, nullptr, true, d_valid, d_req_err, d_set_status);
   return LB_OK;
 }
 
@@ -1723,16 +1756,74 @@ static double ms_since(std::chrono::steady_clock::time_point t) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
 
-static int submit_host(lb_ctx* ctx, Slot& sl, const lb_request_batch* b, uint8_t* out_valid, uint8_t* out_req_err,
-                       uint8_t* out_set_status, bool partial, uint64_t* out_ticket) {
+// The keys each of n_sets descriptors names, counted into pk_off[0 .. n_sets] (running sums),
+// with every bound the expansion's reads depend on checked: the kind, the list and a + len
+// within it, the pool, the bits' bytes.  A BITS set counts the set bits below len.
+static int count_set_keys(lb_ctx* ctx, uint32_t n_sets, const lb_set_keys* sets, uint32_t n_pool, const uint8_t* bits,
+                          uint32_t n_bits_bytes, uint32_t* pk_off) {
+  uint64_t total = 0;
+  pk_off[0] = 0;
+  for (uint32_t i = 0; i < n_sets; i++) {
+    const lb_set_keys& d = sets[i];
+    uint32_t cnt = 0;
+    const char* why = nullptr;
+    if (d.kind == LB_KEYS_DIRECT) {
+      cnt = 1;
+    } else if (d.kind == LB_KEYS_SLICE) {
+      if ((uint64_t)d.a + d.len > n_pool) why = "a + len beyond key_pool";
+      cnt = d.len;
+    } else if (d.kind == LB_KEYS_BITS) {
+      const uint32_t full = d.len / 8, tail = d.len & 7;
+      if (d.list >= LB_INDEX_LISTS || ctx->lists[d.list].n == 0)
+        why = "unknown or unloaded index list";
+      else if ((uint64_t)d.a + d.len > ctx->lists[d.list].n)
+        why = "a + len beyond the index list";
+      else if ((uint64_t)d.bits_off + full + (tail ? 1 : 0) > n_bits_bytes)
+        why = "bits_off + ceil(len / 8) beyond n_bits_bytes";
+      else {
+        const uint8_t* p = bits + d.bits_off;
+        uint32_t k = 0;
+        for (; k + 8 <= full; k += 8) {
+          uint64_t w;
+          memcpy(&w, p + k, 8);
+          cnt += (uint32_t)__builtin_popcountll(w);
+        }
+        for (; k < full; k++) cnt += (uint32_t)__builtin_popcount(p[k]);
+        if (tail) cnt += (uint32_t)__builtin_popcount(p[full] & ((1u << tail) - 1));
+      }
+    } else {
+      why = "unknown kind";
+    }
+    if (!why && (total += cnt) > 0x7fffffffu) why = "more than 2^31 keys";
+    if (why) {
+      ctx->err = "lb_key_source: set " + std::to_string(i) + ": " + why;
+      return LB_ERR_INVALID_ARGUMENT;
+    }
+    pk_off[i + 1] = (uint32_t)total;
+  }
+  return LB_OK;
+}
+
+static IndexLists index_lists(const lb_ctx* ctx) {
+  IndexLists L;
+  for (int i = 0; i < LB_INDEX_LISTS; i++) L.d[i] = ctx->lists[i].d;
+  return L;
+}
+
+// ks (lb_verify_requests_keys*): the sets' keys by descriptor.  The key source is staged behind
+// the package (layout_key_source), counted from the staged copy -- the counts size the indices
+// and are the pk_offsets -- and expanded on the slot's stream in front of the pipeline, which
+// then runs as for a call with pubkey_indices.
+static int submit_host(lb_ctx* ctx, Slot& sl, const lb_request_batch* b, const lb_key_source* ks, uint8_t* out_valid,
+                       uint8_t* out_req_err, uint8_t* out_set_status, bool partial, uint64_t* out_ticket) {
   const auto t0 = std::chrono::steady_clock::now();
   double t_check = 0, t_finish = 0, t_stage = 0, t_pipe = 0;
   const uint32_t nr = b->n_requests, ns = b->n_sets;
   LB_TRY(check_host_batch(ctx, b));
   t_check = ms_since(t0);
   const uint32_t* pk_off = b->pk_offsets;
-  const size_t n_pk = pk_off ? pk_off[ns] : ns;
-  const bool by_index = b->pubkey_indices != nullptr;
+  const size_t n_pk = ks ? 0 : pk_off ? pk_off[ns] : ns;
+  const bool by_index = ks || b->pubkey_indices != nullptr;
   // mixed package: rows of `pubkeys` named by flagged indices (every row < n_rows is staged)
   size_t n_rows = 0;
   if (by_index && b->pubkeys)
@@ -1741,21 +1832,46 @@ static int submit_host(lb_ctx* ctx, Slot& sl, const lb_request_batch* b, uint8_t
       if ((j & LB_PK_ROW_FLAG) && (size_t)(j & LB_PK_ROW_MASK) + 1 > n_rows) n_rows = (j & LB_PK_ROW_MASK) + 1;
     }
   // the package's arrays, declared once (layout_host_call): staged, copied and bound by HostBuf
-  const HostCallShape shape{nr, ns, n_pk, b->sig_offsets[ns], n_rows, pk_off != nullptr, by_index};
+  const HostCallShape shape{nr, ns, n_pk, b->sig_offsets[ns], n_rows, ks || pk_off != nullptr, by_index};
   const HostCallLayout lay = layout_host_call(shape);
+  // (a keys call: HB_PKO is written below from the counts, HB_PK is empty)
   const void* const src[HB_INPUTS] = {b->request_offsets, pk_off,
                                       by_index ? (const void*)b->pubkey_indices : (const void*)b->pubkeys,
                                       b->messages, b->sig_offsets, b->signatures, b->seed, b->pubkeys};
+  KeyShape kshape;
+  KeyLayout klay{};
+  if (ks) {
+    kshape.n_sets = ns;
+    kshape.n_pool = ks->n_pool;
+    kshape.n_bits_bytes = ks->n_bits_bytes;
+    klay = layout_key_source(kshape, lay.end);
+  }
   LB_TRY(finish_slot(ctx, sl));
   pick_streams(ctx, sl);
   t_finish = ms_since(t0);
   if (!partial) borrow_idle_stream(ctx, sl);
-  LB_TRY(ensure_pin(ctx, sl, lay.end));
-  LB_TRY(ensure_ws(ctx, sl, lay.end + pipeline_ws_bytes(ctx, nr, ns)));
-  Slab ws{sl.d_ws, lay.end, sl.ws_cap};
-  char *h = sl.h_pin, *d = sl.d_ws;
+  LB_TRY(ensure_pin(ctx, sl, ks ? klay.in_end : lay.end));
+  char* h = sl.h_pin;
   for (int i = 0; i < HB_INPUTS; i++)
-    if (lay.size[i]) memcpy(h + lay.off[i], src[i], lay.size[i]);
+    if (lay.size[i] && src[i]) memcpy(h + lay.off[i], src[i], lay.size[i]);
+  if (ks) {
+    const void* const ksrc[KB_INPUTS] = {ks->sets, ks->key_pool, ks->bits};
+    for (int i = 0; i < KB_INPUTS; i++)
+      if (klay.size[i]) memcpy(h + klay.off[i], ksrc[i], klay.size[i]);
+    uint32_t* h_pko = slab_at<uint32_t>(h, lay.off[HB_PKO]);
+    const int rc = count_set_keys(ctx, ns, slab_at<const lb_set_keys>(h, klay.off[KB_SETS]), ks->n_pool,
+                                  slab_at<const uint8_t>(h, klay.off[KB_BITS]), ks->n_bits_bytes, h_pko);
+    if (rc != LB_OK) {  // refused with nothing enqueued
+      release_borrowed(sl);
+      return rc;
+    }
+    kshape.n_keys = h_pko[ns];
+    klay = layout_key_source(kshape, lay.end);
+  }
+  const size_t io_end = ks ? klay.end : lay.end;
+  LB_TRY(ensure_ws(ctx, sl, io_end + pipeline_ws_bytes(ctx, nr, ns)));
+  Slab ws{sl.d_ws, io_end, sl.ws_cap};
+  char* d = sl.d_ws;
   t_stage = ms_since(t0);
   LB_TRY(begin_call(ctx, sl));
   sl.dv_valid = slab_at<uint8_t>(d, lay.off[HB_VALID]);
@@ -1769,13 +1885,24 @@ static int submit_host(lb_ctx* ctx, Slot& sl, const lb_request_batch* b, uint8_t
   sl.out_sst = out_set_status;
   sl.out_nr = nr;
   sl.out_ns = out_set_status ? ns : 0;
-  LB_TRY(slot_copy(ctx, sl, d, h, lay.in_bytes, hipMemcpyHostToDevice, sl.st[0]));
+  // (a keys call: one copy up to the end of the key source -- the few output bytes in between
+  // travel with it and are written by the call before anything reads them)
+  LB_TRY(slot_copy(ctx, sl, d, h, ks ? klay.in_end : lay.in_bytes, hipMemcpyHostToDevice, sl.st[0]));
   const auto in8 = [&](HostBuf i) { return slab_at<const uint8_t>(d, lay.off[i]); };
   const auto in32 = [&](HostBuf i) { return slab_at<const uint32_t>(d, lay.off[i]); };
+  const uint32_t* d_pk_idx = by_index ? in32(HB_PK) : nullptr;
+  if (ks) {
+    uint32_t* d_idx = slab_at<uint32_t>(d, klay.off[KB_IDX]);
+    if (ns)
+      LB_STAGE("expand_keys", 0, k_expand_keys, blocks_for(ns, LB_LISTS_TPB / 64), LB_LISTS_TPB, ns,
+               slab_at<const lb_set_keys>(d, klay.off[KB_SETS]), slab_at<const uint32_t>(d, klay.off[KB_POOL]),
+               slab_at<const uint8_t>(d, klay.off[KB_BITS]), index_lists(ctx), in32(HB_PKO), d_idx);
+    d_pk_idx = d_idx;
+  }
   if (nr) {
-    LB_TRY(run_pipeline(ctx, sl, nr, ns, in32(HB_REQ), by_index ? in8(HB_ROWS) : in8(HB_PK), in32(HB_PKO),
-                        by_index ? in32(HB_PK) : nullptr, in8(HB_MSG), in8(HB_SIG), in32(HB_SIGO), in8(HB_SEED),
-                        sl.dv_valid, sl.dv_err, sl.dv_sst, ws, partial));
+    LB_TRY(run_pipeline(ctx, sl, nr, ns, in32(HB_REQ), by_index ? in8(HB_ROWS) : in8(HB_PK), in32(HB_PKO), d_pk_idx,
+                        in8(HB_MSG), in8(HB_SIG), in32(HB_SIGO), in8(HB_SEED), sl.dv_valid, sl.dv_err, sl.dv_sst, ws,
+                        partial));
     t_pipe = ms_since(t0);
   } else if (partial) {
     memset(sl.h_partial, 0, LB_GT_BYTES);
@@ -1786,7 +1913,7 @@ static int submit_host(lb_ctx* ctx, Slot& sl, const lb_request_batch* b, uint8_t
   }
   LB_TRY(end_call_async(ctx, sl));
   *out_ticket = sl.ticket;
-  if (partial) tp_record(ctx, sl.ticket, b, false, out_valid, out_req_err, out_set_status);
+  if (partial) tp_record(ctx, sl.ticket, b, ks, false, out_valid, out_req_err, out_set_status);
   if (host_trace())
     fprintf(stderr, "lb_host_trace sets=%u check=%.3f finish_slot=%.3f stage=%.3f pipeline=%.3f total=%.3f dag=%d slot=%d\n",
             ns, t_check, t_finish, t_stage, t_pipe, ms_since(t0), sl.st[1] != sl.st[0] ? 1 : 0,
@@ -1833,20 +1960,30 @@ int lb_verify_requests_device_async(lb_ctx* ctx, const lb_request_batch* b, uint
   return submit_device(ctx, next_async_slot(ctx), b, d_valid, d_req_err, d_set_status, false, out_ticket);
 }
 
-int lb_verify_requests_async(lb_ctx* ctx, const lb_request_batch* b, uint8_t* out_valid, uint8_t* out_req_err,
-                             uint8_t* out_set_status, uint64_t* out_ticket) {
+// The host-buffer entry points, by pubkeys / indices (ks == nullptr) or by key source
+static int host_async(lb_ctx* ctx, const lb_request_batch* b, const lb_key_source* ks, uint8_t* out_valid,
+                      uint8_t* out_req_err, uint8_t* out_set_status, uint64_t* out_ticket) {
   if (!ctx || !out_ticket) return LB_ERR_INVALID_ARGUMENT;
-  LB_TRY(validate_batch(ctx, b));
+  LB_TRY(validate_host_batch(ctx, b, ks));
   if (!out_valid || !out_req_err) return LB_ERR_INVALID_ARGUMENT;
   LB_HIP(hipSetDevice(ctx->device));
   LB_TRY(sm_pump(ctx));
-  return submit_host(ctx, next_async_slot(ctx), b, out_valid, out_req_err, out_set_status, false, out_ticket);
+  return submit_host(ctx, next_async_slot(ctx), b, ks, out_valid, out_req_err, out_set_status, false, out_ticket);
+}
+int lb_verify_requests_async(lb_ctx* ctx, const lb_request_batch* b, uint8_t* out_valid, uint8_t* out_req_err,
+                             uint8_t* out_set_status, uint64_t* out_ticket) {
+  return host_async(ctx, b, nullptr, out_valid, out_req_err, out_set_status, out_ticket);
+}
+int lb_verify_requests_keys_async(lb_ctx* ctx, const lb_request_batch* b, const lb_key_source* ks, uint8_t* out_valid,
+                                  uint8_t* out_req_err, uint8_t* out_set_status, uint64_t* out_ticket) {
+  if (!ks) return LB_ERR_INVALID_ARGUMENT;
+  return host_async(ctx, b, ks, out_valid, out_req_err, out_set_status, out_ticket);
 }
 
-int lb_verify_requests_partial_async(lb_ctx* ctx, const lb_request_batch* b, uint32_t flags, uint8_t* out_valid,
-                                     uint8_t* out_req_err, uint8_t* out_set_status, uint64_t* out_ticket) {
+static int host_partial(lb_ctx* ctx, const lb_request_batch* b, const lb_key_source* ks, uint32_t flags,
+                        uint8_t* out_valid, uint8_t* out_req_err, uint8_t* out_set_status, uint64_t* out_ticket) {
   if (!ctx || !out_ticket) return LB_ERR_INVALID_ARGUMENT;
-  LB_TRY(validate_batch(ctx, b));
+  LB_TRY(validate_host_batch(ctx, b, ks));
   if (!out_valid || !out_req_err) return LB_ERR_INVALID_ARGUMENT;
   LB_HIP(hipSetDevice(ctx->device));
   LB_TRY(sm_pump(ctx));
@@ -1864,7 +2001,17 @@ int lb_verify_requests_partial_async(lb_ctx* ctx, const lb_request_batch* b, uin
   Slot& sl = next_async_slot(ctx);
   if (flags & LB_BATCH_DEVICE)
     return submit_device(ctx, sl, b, out_valid, out_req_err, out_set_status, true, out_ticket);
-  return submit_host(ctx, sl, b, out_valid, out_req_err, out_set_status, true, out_ticket);
+  return submit_host(ctx, sl, b, ks, out_valid, out_req_err, out_set_status, true, out_ticket);
+}
+int lb_verify_requests_partial_async(lb_ctx* ctx, const lb_request_batch* b, uint32_t flags, uint8_t* out_valid,
+                                     uint8_t* out_req_err, uint8_t* out_set_status, uint64_t* out_ticket) {
+  return host_partial(ctx, b, nullptr, flags, out_valid, out_req_err, out_set_status, out_ticket);
+}
+int lb_verify_requests_keys_partial_async(lb_ctx* ctx, const lb_request_batch* b, const lb_key_source* ks,
+                                          uint8_t* out_valid, uint8_t* out_req_err, uint8_t* out_set_status,
+                                          uint64_t* out_ticket) {
+  if (!ks) return LB_ERR_INVALID_ARGUMENT;
+  return host_partial(ctx, b, ks, 0, out_valid, out_req_err, out_set_status, out_ticket);
 }
 
 int lb_partial_wait(lb_ctx* ctx, uint64_t ticket, uint8_t* out576) {
@@ -1947,9 +2094,11 @@ int lb_verify_requests_finish(lb_ctx* ctx, uint64_t ticket, int merged_ok) {
     const lb_request_batch b = r->batch;
     uint8_t *v = r->valid, *e = r->err, *st = r->sst;
     const bool device = r->device;
+    const lb_key_source keys = r->keys;
+    const lb_key_source* ks = r->by_keys ? &keys : nullptr;
     uint64_t t2 = 0;
     LB_TRY(device ? submit_device(ctx, next_async_slot(ctx), &b, v, e, st, false, &t2)
-                  : submit_host(ctx, next_async_slot(ctx), &b, v, e, st, false, &t2));
+                  : submit_host(ctx, next_async_slot(ctx), &b, ks, v, e, st, false, &t2));
     if (TwoPhaseRec* r2 = tp_find(ctx, ticket)) {
       r2->rerun = t2;
       r2->failed = false;
@@ -2108,10 +2257,10 @@ int lb_verify_requests_device(lb_ctx* ctx, const lb_request_batch* b, uint8_t* d
   return lb_wait(ctx, t, stats);
 }
 
-int lb_verify_requests(lb_ctx* ctx, const lb_request_batch* b, uint8_t* out_valid, uint8_t* out_req_err,
-                       uint8_t* out_set_status, lb_verify_stats* stats) {
+static int host_sync(lb_ctx* ctx, const lb_request_batch* b, const lb_key_source* ks, uint8_t* out_valid,
+                     uint8_t* out_req_err, uint8_t* out_set_status, lb_verify_stats* stats) {
   if (!ctx) return LB_ERR_INVALID_ARGUMENT;
-  LB_TRY(validate_batch(ctx, b));
+  LB_TRY(validate_host_batch(ctx, b, ks));
   if (!out_valid || !out_req_err) return LB_ERR_INVALID_ARGUMENT;
   LB_HIP(hipSetDevice(ctx->device));
   if (b->n_requests == 0) {
@@ -2121,23 +2270,42 @@ int lb_verify_requests(lb_ctx* ctx, const lb_request_batch* b, uint8_t* out_vali
   uint64_t t = 0;
   if (b->n_sets <= ctx->cfg.lp_max_sets && !(lp_lone_rule(ctx->cfg, b->n_sets) && !any_slot_busy(ctx))) {
     // latency path: the priority lane, beside any calls in flight
-    LB_TRY(submit_host(ctx, ctx->prio(), b, out_valid, out_req_err, out_set_status, false, &t));
+    LB_TRY(submit_host(ctx, ctx->prio(), b, ks, out_valid, out_req_err, out_set_status, false, &t));
     return lb_wait(ctx, t, stats);
   }
   BorrowGuard g{ctx};  // synchronous host API: slot 0 (two-stream DAG, lowest latency)
   LB_TRY(borrow_second_stream(ctx, g));
-  LB_TRY(submit_host(ctx, ctx->slots[0], b, out_valid, out_req_err, out_set_status, false, &t));
+  LB_TRY(submit_host(ctx, ctx->slots[0], b, ks, out_valid, out_req_err, out_set_status, false, &t));
   return lb_wait(ctx, t, stats);
 }
+int lb_verify_requests(lb_ctx* ctx, const lb_request_batch* b, uint8_t* out_valid, uint8_t* out_req_err,
+                       uint8_t* out_set_status, lb_verify_stats* stats) {
+  return host_sync(ctx, b, nullptr, out_valid, out_req_err, out_set_status, stats);
+}
+int lb_verify_requests_keys(lb_ctx* ctx, const lb_request_batch* b, const lb_key_source* ks, uint8_t* out_valid,
+                            uint8_t* out_req_err, uint8_t* out_set_status, lb_verify_stats* stats) {
+  if (!ks) return LB_ERR_INVALID_ARGUMENT;
+  return host_sync(ctx, b, ks, out_valid, out_req_err, out_set_status, stats);
+}
 
-int lb_verify_requests_priority_async(lb_ctx* ctx, const lb_request_batch* b, uint8_t* out_valid,
-                                      uint8_t* out_req_err, uint8_t* out_set_status, uint64_t* out_ticket) {
+static int host_priority(lb_ctx* ctx, const lb_request_batch* b, const lb_key_source* ks, uint8_t* out_valid,
+                         uint8_t* out_req_err, uint8_t* out_set_status, uint64_t* out_ticket) {
   if (!ctx || !out_ticket) return LB_ERR_INVALID_ARGUMENT;
-  LB_TRY(validate_batch(ctx, b));
+  LB_TRY(validate_host_batch(ctx, b, ks));
   if (!out_valid || !out_req_err) return LB_ERR_INVALID_ARGUMENT;
   LB_HIP(hipSetDevice(ctx->device));
   LB_TRY(sm_pump(ctx));
-  return submit_host(ctx, ctx->prio(), b, out_valid, out_req_err, out_set_status, false, out_ticket);
+  return submit_host(ctx, ctx->prio(), b, ks, out_valid, out_req_err, out_set_status, false, out_ticket);
+}
+int lb_verify_requests_priority_async(lb_ctx* ctx, const lb_request_batch* b, uint8_t* out_valid,
+                                      uint8_t* out_req_err, uint8_t* out_set_status, uint64_t* out_ticket) {
+  return host_priority(ctx, b, nullptr, out_valid, out_req_err, out_set_status, out_ticket);
+}
+int lb_verify_requests_keys_priority_async(lb_ctx* ctx, const lb_request_batch* b, const lb_key_source* ks,
+                                           uint8_t* out_valid, uint8_t* out_req_err, uint8_t* out_set_status,
+                                           uint64_t* out_ticket) {
+  if (!ks) return LB_ERR_INVALID_ARGUMENT;
+  return host_priority(ctx, b, ks, out_valid, out_req_err, out_set_status, out_ticket);
 }
 // ---- helpers for small host-buffer calls ----------------------------------
 // A synchronous helper call on the idle slot 0: the call declares its buffers (bls_carve.h),
@@ -2333,6 +2501,126 @@ int lb_aggregate_pubkeys_indexed(lb_ctx* ctx, uint32_t n, const uint32_t* indice
     return LB_ERR_INVALID_ARGUMENT;
   }
   return aggregate_pubkeys(ctx, n, nullptr, indices, out96, out_status);
+}
+
+// ---- device-resident index lists (shufflings, sync committees) -------------------
+// Room for n entries in list L; the calls in flight, which may read it, have retired
+static int list_reserve(lb_ctx* ctx, lb_ctx::IndexList& L, uint32_t n) {
+  if (n <= L.cap) return LB_OK;
+  const uint32_t cap = n < 1024 ? 1024 : n;
+  uint32_t* d = nullptr;
+  if (hipMalloc(&d, sizeof(uint32_t) * (size_t)cap) != hipSuccess) {
+    ctx->err = "hipMalloc index list failed";
+    return LB_ERR_OUT_OF_MEMORY;
+  }
+  if (L.d) LB_HIP(hipFree(L.d));
+  L.d = d;
+  L.cap = cap;
+  L.n = 0;
+  return LB_OK;
+}
+
+int lb_index_list_put(lb_ctx* ctx, uint32_t list, uint32_t n, const uint32_t* indices) {
+  if (!ctx || list >= LB_INDEX_LISTS || (n && !indices)) return LB_ERR_INVALID_ARGUMENT;
+  LB_HIP(hipSetDevice(ctx->device));
+  LB_TRY(helper_slot(ctx));  // calls in flight read the lists
+  lb_ctx::IndexList& L = ctx->lists[list];
+  if (n) {
+    LB_TRY(list_reserve(ctx, L, n));
+    LB_HIP(hipMemcpyAsync(L.d, indices, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    LB_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  L.n = n;
+  return LB_OK;
+}
+
+int lb_index_list_shuffle(lb_ctx* ctx, uint32_t list, uint32_t n, const uint32_t* active, const uint8_t* seed32,
+                          uint32_t* out_shuffling) {
+  if (!ctx || list >= LB_INDEX_LISTS || (n && !active) || !seed32) return LB_ERR_INVALID_ARGUMENT;
+  if (n > LB_SHUFFLE_MAX) {
+    ctx->err = "lb_index_list_shuffle: more than LB_SHUFFLE_MAX indices";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  ctx->n_stages = 0;
+  if (n <= 1) {  // nothing to swap
+    LB_TRY(lb_index_list_put(ctx, list, n, active));
+    if (n && out_shuffling) out_shuffling[0] = active[0];
+    return LB_OK;
+  }
+  LB_HIP(hipSetDevice(ctx->device));
+  LB_TRY(helper_slot(ctx));
+  lb_ctx::IndexList& L = ctx->lists[list];
+  LB_TRY(list_reserve(ctx, L, n));
+  for (hipEvent_t& e : ctx->list_ev)
+    if (!e) LB_HIP(hipEventCreate(&e));
+  const uint32_t n_digests = LB_SHUFFLE_ROUNDS * ((n + 255) / 256);
+  HelperCall c(ctx);
+  auto d_active = c.in(active, n);
+  auto d_seed = c.in(seed32, 32);
+  auto d_pivots = c.scratch<uint32_t>(LB_SHUFFLE_ROUNDS);
+  auto d_table = c.scratch<uint32_t>((size_t)n_digests * 8);  // [round][ceil(n/256)] digests
+  LB_TRY(c.begin());
+  const bool timed = ctx->ccfg.stage_events;
+  if (timed) LB_HIP(hipEventRecord(ctx->list_ev[0], ctx->stream));
+  LB_LAUNCH(k_shuffle_sources, blocks_for(n_digests, LB_LISTS_TPB), LB_LISTS_TPB, n, d_seed, d_pivots, d_table);
+  LB_LAUNCH(k_shuffle_apply, blocks_for(n, LB_LISTS_TPB), LB_LISTS_TPB, n, (const uint32_t*)d_pivots,
+            (const uint8_t*)(uint32_t*)d_table, d_active, L.d);
+  if (timed) LB_HIP(hipEventRecord(ctx->list_ev[1], ctx->stream));
+  L.n = 0;  // (until the kernels are known to have run)
+  if (out_shuffling)
+    LB_HIP(hipMemcpyAsync(out_shuffling, L.d, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  LB_TRY(c.end());
+  L.n = n;
+  if (timed) {
+    LB_HIP(hipEventElapsedTime(&ctx->stage_ms[0], ctx->list_ev[0], ctx->list_ev[1]));
+    ctx->stage_name[0] = "shuffle";
+    ctx->stage_ops[0] = 0;
+    ctx->n_stages = 1;
+  }
+  return LB_OK;
+}
+
+int lb_index_list_size(const lb_ctx* ctx, uint32_t list, uint32_t* out_n) {
+  if (!ctx || list >= LB_INDEX_LISTS || !out_n) return LB_ERR_INVALID_ARGUMENT;
+  *out_n = ctx->lists[list].n;
+  return LB_OK;
+}
+
+int lb_index_list_read(lb_ctx* ctx, uint32_t list, uint32_t first, uint32_t n, uint32_t* out) {
+  if (!ctx || list >= LB_INDEX_LISTS || (n && !out) || (uint64_t)first + n > ctx->lists[list].n)
+    return LB_ERR_INVALID_ARGUMENT;
+  if (n == 0) return LB_OK;
+  LB_HIP(hipSetDevice(ctx->device));
+  LB_HIP(hipMemcpyAsync(out, ctx->lists[list].d + first, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost,
+                        ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  return LB_OK;
+}
+
+int lb_expand_set_keys(lb_ctx* ctx, uint32_t n_sets, const lb_key_source* ks, uint32_t* out_pk_offsets,
+                       uint32_t* out_indices, uint32_t max_indices) {
+  if (!ctx || !ks || !out_pk_offsets || (n_sets && !ks->sets) || (ks->n_pool && !ks->key_pool) ||
+      (ks->n_bits_bytes && !ks->bits) || (max_indices && !out_indices))
+    return LB_ERR_INVALID_ARGUMENT;
+  std::vector<uint32_t> pk_off((size_t)n_sets + 1);
+  LB_TRY(count_set_keys(ctx, n_sets, ks->sets, ks->n_pool, ks->bits, ks->n_bits_bytes, pk_off.data()));
+  const uint32_t n_keys = pk_off[n_sets];
+  if (n_keys > max_indices) {
+    ctx->err = "lb_expand_set_keys: the sets expand to more than max_indices";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  memcpy(out_pk_offsets, pk_off.data(), sizeof(uint32_t) * pk_off.size());
+  if (n_sets == 0) return LB_OK;
+  HelperCall c(ctx);
+  auto d_sets = c.in(ks->sets, n_sets);
+  auto d_pool = c.in(ks->key_pool, ks->n_pool);
+  auto d_bits = c.in(ks->bits, ks->n_bits_bytes);
+  auto d_off = c.in(pk_off.data(), pk_off.size());
+  auto d_idx = c.out(out_indices, n_keys);
+  LB_TRY(c.begin());
+  LB_LAUNCH(k_expand_keys, blocks_for(n_sets, LB_LISTS_TPB / 64), LB_LISTS_TPB, n_sets, d_sets, d_pool, d_bits,
+            index_lists(ctx), d_off, d_idx);
+  return c.end();
 }
 
 // ---- signing roots -----------------------------------------------------------

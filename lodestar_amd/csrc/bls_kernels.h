@@ -339,4 +339,24 @@ __global__ void __launch_bounds__(TPB, LB_W_TAIL) k_req_join(uint32_t n_req, uin
                                                            fp12* __restrict__ F, const uint8_t* __restrict__ skip);
 __global__ void __launch_bounds__(TPB) k_msm_load(uint32_t n, const uint8_t* __restrict__ in192, g2j* __restrict__ out,
                                                   uint8_t* __restrict__ status);
+// device-resident index lists (k_lists.hip): the swap-or-not shuffle and the expansion of
+// set descriptors into validator indices.  The context's lists as a kernel argument:
+struct IndexLists {
+  const uint32_t* d[LB_INDEX_LISTS];
+};
+// bytes of one round's row of the source table: ceil(n / 256) digests of 32 bytes
+inline constexpr size_t shuffle_row_bytes(uint32_t n) { return ((size_t)n + 255) / 256 * 32; }
+static constexpr uint32_t LB_LISTS_TPB = 256;
+__global__ void __launch_bounds__(LB_LISTS_TPB) k_shuffle_sources(uint32_t n, const uint8_t* __restrict__ seed,
+                                                                  uint32_t* __restrict__ pivots,
+                                                                  uint32_t* __restrict__ table);
+__global__ void __launch_bounds__(LB_LISTS_TPB) k_shuffle_apply(uint32_t n, const uint32_t* __restrict__ pivots,
+                                                                const uint8_t* __restrict__ table,
+                                                                const uint32_t* __restrict__ active,
+                                                                uint32_t* __restrict__ out);
+__global__ void __launch_bounds__(LB_LISTS_TPB) k_expand_keys(uint32_t n_sets, const lb_set_keys* __restrict__ sets,
+                                                              const uint32_t* __restrict__ pool,
+                                                              const uint8_t* __restrict__ bits, IndexLists lists,
+                                                              const uint32_t* __restrict__ pk_off,
+                                                              uint32_t* __restrict__ idx);
 }  // namespace lb

@@ -180,7 +180,107 @@ async function packRequestsAsync(requests, seed, keyMap, slice = 8192, timing = 
   return r.value;
 }
 
+// lb_set_keys kinds (include/lodestar_bls.h)
+const LB_KEYS_DIRECT = 0;
+const LB_KEYS_SLICE = 1;
+const LB_KEYS_BITS = 2;
+
+/** The keys of every set as descriptors -- five words per set (kind, list, a, len, bitsOff),
+ * the pool of the aggregate sets' explicit indices and the bits sets' bytes -- when every key
+ * is a validator index or the set is {type: "bits", list, start, length, bits}; null when
+ * some key has to travel by its bytes. */
+function packSetKeys(requests, keyMap) {
+  let nSets = 0;
+  let nPool = 0;
+  let nBits = 0;
+  for (const req of requests) {
+    for (const s of req) {
+      nSets++;
+      if (s.type === "bits") {
+        if (!(s.bits instanceof Uint8Array) || s.bits.length < ((s.length + 7) >>> 3))
+          throw new TypeError("bits set: `bits` must hold ceil(length / 8) bytes");
+        nBits += (s.length + 7) >>> 3;
+      } else if (s.type === "aggregate") nPool += (s.pubkeys || []).length;
+    }
+  }
+  const setKeys = new Uint32Array(5 * nSets);
+  const keyPool = new Uint32Array(nPool);
+  const keyBits = new Uint8Array(nBits);
+  let i = 0;
+  let p = 0;
+  let b = 0;
+  for (const req of requests) {
+    for (const s of req) {
+      const o = 5 * i++;
+      if (s.type === "bits") {
+        const nb = (s.length + 7) >>> 3;
+        setKeys.set([LB_KEYS_BITS, s.list, s.start, s.length, b], o);
+        keyBits.set(s.bits.subarray(0, nb), b);
+        b += nb;
+      } else if (s.type === "aggregate") {
+        const ks = s.pubkeys || [];
+        setKeys.set([LB_KEYS_SLICE, 0, p, ks.length, 0], o);
+        for (const pk of ks) {
+          const ix = keyIndex(pk, keyMap);
+          if (ix < 0) return null;
+          keyPool[p++] = ix;
+        }
+      } else {
+        const ix = keyIndex(s.pubkey, keyMap);
+        if (ix < 0) return null;
+        setKeys.set([LB_KEYS_DIRECT, 0, ix, 0, 0], o);
+      }
+    }
+  }
+  return {setKeys, keyPool, keyBits};
+}
+
+/** A bits set as today's aggregate set, from the host's copy of the list (the package holds a
+ * key that travels by its bytes, so it cannot go as descriptors). */
+function expandBitsSet(s, keyMap) {
+  const list = keyMap && keyMap.lbLists ? keyMap.lbLists.get(s.list) : undefined;
+  if (!list || s.start + s.length > list.length)
+    throw new TypeError("bits set: index list " + s.list + " is not loaded (syncShuffling / putIndexList)");
+  const pubkeys = [];
+  for (let j = 0; j < s.length; j++) if ((s.bits[j >>> 3] >>> (j & 7)) & 1) pubkeys.push({index: list[s.start + j]});
+  return {type: "aggregate", pubkeys, signingRoot: s.signingRoot, signature: s.signature};
+}
+
 function* packRequestsGen(requests, seed, keyMap, slice) {
+  // a package with bits sets: as set descriptors when every other key is a validator index
+  // (the GPU expands bits to indices), else today's form with the bits sets expanded here
+  if (requests.some((req) => req.some((s) => s.type === "bits"))) {
+    const ks = packSetKeys(requests, keyMap);
+    if (ks) {
+      let n = 0;
+      let bytes = 0;
+      for (const req of requests) {
+        for (const s of req) {
+          if (!(s.signingRoot instanceof Uint8Array) || s.signingRoot.length !== 32)
+            throw new TypeError("signingRoot must be 32 bytes");
+          bytes += s.signature.length;
+          n++;
+        }
+      }
+      const reqOff = new Uint32Array(requests.length + 1);
+      const sigOff = new Uint32Array(n + 1);
+      const messages = new Uint8Array(32 * n);
+      const signatures = new Uint8Array(bytes);
+      let i = 0;
+      let so = 0;
+      for (let r = 0; r < requests.length; r++) {
+        for (const s of requests[r]) {
+          messages.set(s.signingRoot, 32 * i);
+          signatures.set(s.signature, so);
+          so += s.signature.length;
+          sigOff[++i] = so;
+        }
+        reqOff[r + 1] = i;
+      }
+      return {requestOffsets: reqOff, messages, signatures, sigOffsets: sigOff, seed, ...ks};
+    }
+    requests = requests.map((req) => req.map((s) => (s.type === "bits" ? expandBitsSet(s, keyMap) : s)));
+  }
   // pass 1: sizes; pass 2: every key's index (one identity-map lookup per key) or its
   // encoding; pass 3: the arrays.  Between slices of `slice` sets the caller may yield.
   let nSets = 0;
@@ -584,6 +684,27 @@ class BlsGpuVerifier {
     return this.tableSize;
   }
 
+  /** computeEpochShuffling's unshuffleList (state-transition/src/util/epochShuffling.ts:62-101)
+   * on the GPU: index list `listId` of every GPU becomes unshuffleList(activeIndices, seed),
+   * which also resolves (Uint32Array) for the node's EpochShuffling.  Sets of type "bits"
+   * ({list, start, length, bits, signingRoot, signature}) then name a committee as a slice of
+   * it and ship the attestation's aggregation bits instead of the attesting indices. */
+  async syncShuffling(listId, activeIndices, seed) {
+    const active = activeIndices instanceof Uint32Array ? activeIndices : Uint32Array.from(activeIndices);
+    const outs = await Promise.all(this.backends.map((b) => b.indexListShuffle(listId, active, seed)));
+    this.keyMap.lbLists = this.keyMap.lbLists || new Map();
+    this.keyMap.lbLists.set(listId, outs[0]);
+    return outs[0];
+  }
+
+  /** Store validator indices as given (a sync committee's 512) as index list `listId`. */
+  async putIndexList(listId, indices) {
+    const ix = indices instanceof Uint32Array ? indices : Uint32Array.from(indices);
+    await Promise.all(this.backends.map((b) => b.indexListPut(listId, ix)));
+    this.keyMap.lbLists = this.keyMap.lbLists || new Map();
+    this.keyMap.lbLists.set(listId, ix);
+  }
+
   /** pubkeyCache.syncPubkeys (pubkeyCache.ts:56-77) for the GPUs: mirror the entries of
    * index2pubkey (PublicKey objects) not mirrored yet -- index2pubkey[i] maps to table
    * entry base + i, where base is the table size at the first call -- and return the
@@ -956,6 +1077,20 @@ class BlsGpuSingleThreadVerifier {
     this.tableSize = 0;
     this.mirror = null;
   }
+  /** as BlsGpuVerifier.syncShuffling / putIndexList, on this verifier's one GPU */
+  async syncShuffling(listId, activeIndices, seed) {
+    const active = activeIndices instanceof Uint32Array ? activeIndices : Uint32Array.from(activeIndices);
+    const out = await this.backend.indexListShuffle(listId, active, seed);
+    this.keyMap.lbLists = this.keyMap.lbLists || new Map();
+    this.keyMap.lbLists.set(listId, out);
+    return out;
+  }
+  async putIndexList(listId, indices) {
+    const ix = indices instanceof Uint32Array ? indices : Uint32Array.from(indices);
+    await this.backend.indexListPut(listId, ix);
+    this.keyMap.lbLists = this.keyMap.lbLists || new Map();
+    this.keyMap.lbLists.set(listId, ix);
+  }
   /** as BlsGpuVerifier.syncPubkeys / syncIndex2pubkey, on this verifier's one GPU */
   async syncPubkeys(keys, pkLen = 48) {
     this.tableSize = await syncKeyTables([this.backend], this.keyMap, keys, pkLen);
@@ -1129,6 +1264,7 @@ async function combineShards(backends, sizes, packShard) {
 }
 
 module.exports = {
+  packSetKeys,
   BlsGpuVerifier,
   BlsGpuSingleThreadVerifier,
   QueueError,

@@ -31,7 +31,20 @@ export type AggregatedSignatureSet = {
   signingRoot: Uint8Array;
   signature: Uint8Array;
 };
-export type ISignatureSet = SingleSignatureSet | AggregatedSignatureSet;
+/** An aggregate set over a committee held on the GPU: its keys are list[start + j] for every set
+ * bit j < length of `bits` (SSZ bit order, any delimiter bit stripped), `list` an index list
+ * loaded with syncShuffling / putIndexList -- the attestation as it arrived, in place of
+ * aggregationBits.intersectValues(getBeaconCommittee(slot, index)) (epochCache.ts:684-685). */
+export type BitsSignatureSet = {
+  type: "bits";
+  list: number;
+  start: number;
+  length: number;
+  bits: Uint8Array;
+  signingRoot: Uint8Array;
+  signature: Uint8Array;
+};
+export type ISignatureSet = SingleSignatureSet | AggregatedSignatureSet | BitsSignatureSet;
 
 /** interface.ts:4-23 */
 export type VerifySignatureOpts = {
@@ -65,6 +78,12 @@ export type PackedRequests = {
   sigOffsets: Uint32Array;
   seed: Uint8Array;
   batchable?: Uint8Array;
+  /** keys by descriptor (lb_key_source), instead of pkOffsets / pubkeys / pubkeyIndices: five
+   * words per set (lb_set_keys: kind, list, a, len, bitsOff), the SLICE sets' indices, the BITS
+   * sets' bytes */
+  setKeys?: Uint32Array;
+  keyPool?: Uint32Array;
+  keyBits?: Uint8Array;
 };
 
 export type SameMessageBatch = {
@@ -113,6 +132,10 @@ export interface GpuBackend {
     opts?: {noCheck?: boolean}
   ): Promise<{signatures: Uint8Array; badIndex: Int32Array}>;
   syncPubkeys?(keys: Uint8Array, pkLen: number): Promise<number>;
+  /** lb_index_list_put: resolves to the list's size */
+  indexListPut?(listId: number, indices: Uint32Array): Promise<number>;
+  /** lb_index_list_shuffle: resolves to unshuffleList(activeIndices, seed), which list `listId` now holds */
+  indexListShuffle?(listId: number, activeIndices: Uint32Array, seed: Uint8Array): Promise<Uint32Array>;
   aggregatePubkeys?(keys: Uint8Array | Uint32Array): Promise<Uint8Array>;
   /** KZG_SETUP_G2_MONOMIAL[1], 96 bytes compressed; a refused point rejects and keeps the old setup */
   kzgLoadSetup?(g2Tau: Uint8Array): Promise<void>;
@@ -191,6 +214,11 @@ export class BlsGpuVerifier implements IBlsVerifier {
   /** Append keys to every GPU's pubkey table (pubkeyCache.ts:56-77); PublicKey objects are
    * serialized once here and then ship as their table index.  Returns the table size. */
   syncPubkeys(keys: (Uint8Array | PublicKeyLike)[], pkLen?: 48 | 96): Promise<number>;
+  /** computeEpochShuffling's unshuffleList on the GPU (8 list ids, 0..7): every GPU keeps the
+   * shuffling as index list `listId`; resolves to it for the node's EpochShuffling */
+  syncShuffling(listId: number, activeIndices: Uint32Array | number[], seed: Uint8Array): Promise<Uint32Array>;
+  /** indices as given (a sync committee's 512) as index list `listId` */
+  putIndexList(listId: number, indices: Uint32Array | number[]): Promise<void>;
   /** pubkeyCache.syncPubkeys for the GPUs: mirror index2pubkey's new entries (incremental);
    * returns the number of entries mirrored. */
   syncIndex2pubkey(index2pubkey: PublicKeyLike[]): Promise<number>;
@@ -226,6 +254,11 @@ export class BlsGpuSingleThreadVerifier implements IBlsVerifier {
     addon?: AddonModule;
   });
   syncPubkeys(keys: (Uint8Array | PublicKeyLike)[], pkLen?: 48 | 96): Promise<number>;
+  /** computeEpochShuffling's unshuffleList on the GPU (8 list ids, 0..7): every GPU keeps the
+   * shuffling as index list `listId`; resolves to it for the node's EpochShuffling */
+  syncShuffling(listId: number, activeIndices: Uint32Array | number[], seed: Uint8Array): Promise<Uint32Array>;
+  /** indices as given (a sync committee's 512) as index list `listId` */
+  putIndexList(listId: number, indices: Uint32Array | number[]): Promise<void>;
   syncIndex2pubkey(index2pubkey: PublicKeyLike[]): Promise<number>;
   verifySignatureSets(sets: ISignatureSet[]): Promise<boolean>;
   verifySignatureSetsSameMessage(

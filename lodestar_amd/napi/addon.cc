@@ -174,7 +174,7 @@ void check_offsets(const std::vector<uint32_t>& off, size_t n, uint32_t last, co
 
 // ---- tasks ---------------------------------------------------------------------
 enum class Kind {
-  Verify, Partial, Finish, SameMessage, SyncPubkeys, AggPubkeys, AggSigGroups, GtCheck, KzgLoad, KzgVerify, KzgLoadG1, KzgCommit, KzgProve, KzgPoint, Close
+  Verify, Partial, Finish, SameMessage, SyncPubkeys, AggPubkeys, AggSigGroups, GtCheck, KzgLoad, KzgVerify, KzgLoadG1, KzgCommit, KzgProve, KzgPoint, IndexListPut, IndexListShuffle, Close
 };
 
 struct Task {
@@ -189,6 +189,14 @@ struct Task {
   std::vector<napi_ref> refs;
   bool has_pk_off = false, by_index = false, has_batchable = false, mixed = false;
   bool prio = false;  // verifyRequests(batch, {priority: true}): the device's priority lane
+  // verifyRequests({setKeys, keyPool, keyBits, ...}): the sets' keys by descriptor (lb_key_source);
+  // set_keys holds five words per set (lb_set_keys: kind, list, a, len, bits_off)
+  bool by_keys = false;
+  std::vector<uint32_t> set_keys, key_pool;
+  std::vector<uint8_t> key_bits;
+  // indexListPut / indexListShuffle: the list id, the indices in (pk_idx) and the shuffling out
+  uint32_t list_id = 0;
+  std::vector<uint32_t> list_out;
   // verifySameMessage(batch, {aggregate, mask}): the jobs' aggregate signatures as well;
   // aggregateSignatureGroups: groups in job_off, noCheck in no_check
   bool agg = false, has_mask = false, no_check = false;
@@ -234,6 +242,21 @@ void parse_requests(napi_env env, napi_value obj, Task& t) {
   check_offsets(t.sig_off, t.n_sets, (uint32_t)t.v_signatures.size(), "sigOffsets");
   req_typed(env, obj, "seed", napi_uint8_array, t.seed);
   if (t.seed.size() != 32) throw ArgError{"seed must be 32 bytes"};
+  t.by_keys = opt_typed(env, obj, "setKeys", napi_uint32_array, t.set_keys);
+  if (t.by_keys) {
+    // keys by descriptor: nothing else names a key (the library checks every bound at submit)
+    napi_value x;
+    if (has_prop(env, obj, "pkOffsets", &x) || has_prop(env, obj, "pubkeyIndices", &x) || has_prop(env, obj, "pubkeys", &x))
+      throw ArgError{"setKeys excludes pubkeys, pkOffsets and pubkeyIndices"};
+    if (t.set_keys.size() != (size_t)t.n_sets * 5) throw ArgError{"setKeys: five words per set"};
+    opt_typed(env, obj, "keyPool", napi_uint32_array, t.key_pool);
+    opt_typed(env, obj, "keyBits", napi_uint8_array, t.key_bits);
+    t.has_batchable = opt_typed(env, obj, "batchable", napi_uint8_array, t.batchable);
+    if (t.has_batchable && t.batchable.size() != t.n_req) throw ArgError{"batchable: one flag per request"};
+    if (t.v_signatures.empty()) t.v_signatures.own.assign(1, 0);
+    if (t.v_messages.empty()) t.v_messages.own.assign(1, 0);
+    return;
+  }
   t.has_pk_off = opt_typed(env, obj, "pkOffsets", napi_uint32_array, t.pk_off);
   if (t.has_pk_off) check_offsets(t.pk_off, t.n_sets, UINT32_MAX, "pkOffsets");
   const size_t n_pk = t.has_pk_off ? t.pk_off[t.n_sets] : t.n_sets;
@@ -276,7 +299,7 @@ lb_request_batch batch_of(Task& t) {
   b.n_sets = t.n_sets;
   b.request_offsets = t.req_off.data();
   b.request_batchable = t.has_batchable ? t.batchable.data() : nullptr;
-  b.pubkeys = (!t.by_index || t.mixed) ? t.v_pubkeys.data() : nullptr;
+  b.pubkeys = t.by_keys ? nullptr : (!t.by_index || t.mixed) ? t.v_pubkeys.data() : nullptr;
   b.pk_offsets = t.has_pk_off ? t.pk_off.data() : nullptr;
   b.messages = t.v_messages.data();
   b.signatures = t.v_signatures.data();
@@ -284,6 +307,34 @@ lb_request_batch batch_of(Task& t) {
   b.seed = t.seed.data();
   b.pubkey_indices = t.by_index ? t.v_pk_idx.data() : nullptr;
   return b;
+}
+
+static_assert(sizeof(lb_set_keys) == 5 * sizeof(uint32_t), "setKeys rows are lb_set_keys");
+lb_key_source keys_of(Task& t) {
+  static const uint32_t none32 = 0;
+  static const uint8_t none8 = 0;
+  lb_key_source k{};
+  k.sets = reinterpret_cast<const lb_set_keys*>(t.set_keys.empty() ? &none32 : t.set_keys.data());
+  k.key_pool = t.key_pool.empty() ? &none32 : t.key_pool.data();
+  k.n_pool = (uint32_t)t.key_pool.size();
+  k.bits = t.key_bits.empty() ? &none8 : t.key_bits.data();
+  k.n_bits_bytes = (uint32_t)t.key_bits.size();
+  return k;
+}
+
+// Submit a verify task's call in the form its batch came in: 0 async, 1 priority, 2 two-phase
+int submit_call(lb_ctx* ctx, Task& t, int mode) {
+  lb_request_batch b = batch_of(t);
+  uint8_t *v = t.valid.data(), *e = t.err.data(), *s = t.sst.data();
+  if (t.by_keys) {
+    const lb_key_source k = keys_of(t);
+    return mode == 1   ? lb_verify_requests_keys_priority_async(ctx, &b, &k, v, e, s, &t.ticket)
+           : mode == 2 ? lb_verify_requests_keys_partial_async(ctx, &b, &k, v, e, s, &t.ticket)
+                       : lb_verify_requests_keys_async(ctx, &b, &k, v, e, s, &t.ticket);
+  }
+  return mode == 1   ? lb_verify_requests_priority_async(ctx, &b, v, e, s, &t.ticket)
+         : mode == 2 ? lb_verify_requests_partial_async(ctx, &b, 0, v, e, s, &t.ticket)
+                     : lb_verify_requests_async(ctx, &b, v, e, s, &t.ticket);
 }
 
 void alloc_outputs(Task& t) {
@@ -370,6 +421,17 @@ void lane_loop(Context* c) {
       complete(c, t);
       continue;
     }
+    if (t->kind == Kind::IndexListPut || t->kind == Kind::IndexListShuffle) {
+      // (the lane's lists mirror ctx's, as its pubkey table does: a shuffling arrives computed)
+      const std::vector<uint32_t>& ix = t->kind == Kind::IndexListPut ? t->pk_idx : t->list_out;
+      if (c->lane_ok && lb_index_list_put(c->lctx, t->list_id, t->n_keys, ix.data()) != LB_OK) {
+        c->lane_ok = false;
+        fprintf(stderr, "lodestar_bls: latency lane retired (its index lists could not follow: %s); priority "
+                        "calls run on the main context\n", lb_last_error(c->lctx));
+      }
+      complete(c, t);
+      continue;
+    }
     if (!c->lane_ok) {  // a priority call queued here before the lane retired: back to ctx
       {
         std::lock_guard<std::mutex> lk(c->mu);
@@ -382,8 +444,7 @@ void lane_loop(Context* c) {
     }
     t->t_start = now_ns();
     alloc_outputs(*t);
-    lb_request_batch b = batch_of(*t);
-    int rc = lb_verify_requests_priority_async(c->lctx, &b, t->valid.data(), t->err.data(), t->sst.data(), &t->ticket);
+    int rc = submit_call(c->lctx, *t, 1);
     t->t_submitted = now_ns();
     if (rc == LB_OK) {
       t->t_retire = now_ns();
@@ -510,11 +571,7 @@ void worker_loop(Context* c) {
     switch (t->kind) {
       case Kind::Verify: {
         alloc_outputs(*t);
-        lb_request_batch b = batch_of(*t);
-        const int rc = t->prio ? lb_verify_requests_priority_async(c->ctx, &b, t->valid.data(), t->err.data(),
-                                                                   t->sst.data(), &t->ticket)
-                               : lb_verify_requests_async(c->ctx, &b, t->valid.data(), t->err.data(),
-                                                          t->sst.data(), &t->ticket);
+        const int rc = submit_call(c->ctx, *t, t->prio ? 1 : 0);
         t->t_submitted = now_ns();
         if (rc != LB_OK) {
           fail(t, rc, c->ctx);
@@ -530,9 +587,7 @@ void worker_loop(Context* c) {
         Task* call = new Task(std::move(*t));
         call->deferred = nullptr;
         alloc_outputs(*call);
-        lb_request_batch b = batch_of(*call);
-        int rc = lb_verify_requests_partial_async(c->ctx, &b, 0, call->valid.data(), call->err.data(),
-                                                  call->sst.data(), &call->ticket);
+        int rc = submit_call(c->ctx, *call, 2);
         t->out_bytes.assign(LB_GT_BYTES, 0);
         if (rc == LB_OK) rc = lb_partial_wait(c->ctx, call->ticket, t->out_bytes.data());
         if (rc != LB_OK) {
@@ -613,6 +668,29 @@ void worker_loop(Context* c) {
             c->lcv.notify_one();
             break;
           }
+        }
+        complete(c, t);
+        break;
+      }
+      case Kind::IndexListPut:
+      case Kind::IndexListShuffle: {
+        int rc;
+        if (t->kind == Kind::IndexListPut) {
+          rc = lb_index_list_put(c->ctx, t->list_id, t->n_keys, t->pk_idx.data());
+        } else {
+          t->list_out.assign(t->n_keys ? t->n_keys : 1, 0);
+          rc = lb_index_list_shuffle(c->ctx, t->list_id, t->n_keys, t->pk_idx.data(), t->seed.data(),
+                                     t->list_out.data());
+        }
+        if (rc != LB_OK) {
+          fail(t, rc, c->ctx);
+        } else if (c->lctx && c->lane_ok) {  // the same list into the latency lane's context, then resolve
+          {
+            std::lock_guard<std::mutex> lk(c->lmu);
+            c->lqueue.push_back(t);
+          }
+          c->lcv.notify_one();
+          break;
         }
         complete(c, t);
         break;
@@ -862,6 +940,12 @@ void call_js(napi_env env, napi_value /*cb*/, void* context, void* data) {
         break;
       case Kind::AggPubkeys:
         result = make_u8(env, t->out_bytes.data(), LB_PUBKEY_BYTES);
+        break;
+      case Kind::IndexListPut:
+        napi_create_uint32(env, t->n_keys, &result);
+        break;
+      case Kind::IndexListShuffle:
+        result = make_words(env, napi_uint32_array, t->list_out.data(), t->n_keys);
         break;
       case Kind::GtCheck:
         napi_get_boolean(env, t->i32 != 0, &result);
@@ -1132,6 +1216,38 @@ napi_value SyncPubkeys(napi_env env, napi_callback_info info) {
     return rejected(env, e.msg);
   }
   return submit(env, c, t);
+}
+
+// indexListPut(listId, indices: Uint32Array) -> Promise<number>;
+// indexListShuffle(listId, activeIndices: Uint32Array, seed: Uint8Array(32)) -> Promise<Uint32Array>
+napi_value m_index_list(napi_env env, napi_callback_info info, Kind kind) {
+  size_t argc = 3;
+  napi_value argv[3];
+  Context* c = unwrap(env, info, &argc, argv);
+  Task* t = new Task();
+  t->kind = kind;
+  try {
+    const bool shuffle = kind == Kind::IndexListShuffle;
+    if (!c || argc < (shuffle ? 3u : 2u))
+      throw ArgError{shuffle ? "indexListShuffle(listId, activeIndices: Uint32Array, seed: Uint8Array)"
+                             : "indexListPut(listId, indices: Uint32Array)"};
+    if (napi_get_value_uint32(env, argv[0], &t->list_id) != napi_ok) throw ArgError{"listId must be a number"};
+    typed(env, argv[1], napi_uint32_array, "indices", t->pk_idx);
+    t->n_keys = (uint32_t)t->pk_idx.size();
+    if (t->pk_idx.empty()) t->pk_idx.push_back(0);
+    if (shuffle) {
+      typed(env, argv[2], napi_uint8_array, "seed", t->seed);
+      if (t->seed.size() != 32) throw ArgError{"seed must be 32 bytes"};
+    }
+  } catch (const ArgError& e) {
+    delete t;
+    return rejected(env, e.msg);
+  }
+  return submit(env, c, t);
+}
+napi_value IndexListPut(napi_env env, napi_callback_info info) { return m_index_list(env, info, Kind::IndexListPut); }
+napi_value IndexListShuffle(napi_env env, napi_callback_info info) {
+  return m_index_list(env, info, Kind::IndexListShuffle);
 }
 
 napi_value AggregatePubkeys(napi_env env, napi_callback_info info) {
@@ -1423,6 +1539,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"gtCheck", nullptr, GtCheck, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"verifySameMessage", nullptr, VerifySameMessage, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"syncPubkeys", nullptr, SyncPubkeys, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"indexListPut", nullptr, IndexListPut, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"indexListShuffle", nullptr, IndexListShuffle, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"aggregatePubkeys", nullptr, AggregatePubkeys, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"aggregateSignatureGroups", nullptr, AggregateSignatureGroups, nullptr, nullptr, nullptr, napi_default,
        nullptr},

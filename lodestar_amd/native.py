@@ -48,7 +48,19 @@ EXPORTED_SYMBOLS = (
     "lb_kzg_blob_challenges", "lb_kzg_evaluate",
     "lb_kzg_load_setup_g1", "lb_kzg_setup_g1_loaded", "lb_kzg_blob_commitments", "lb_kzg_blob_proofs",
     "lb_kzg_compute_proofs", "lb_kzg_g1_lincomb",
+    "lb_index_list_put", "lb_index_list_shuffle", "lb_index_list_size", "lb_index_list_read",
+    "lb_verify_requests_keys", "lb_verify_requests_keys_async", "lb_verify_requests_keys_priority_async",
+    "lb_verify_requests_keys_partial_async", "lb_expand_set_keys",
 )
+
+# device-resident index lists and set keys by descriptor (lb_index_list_*, lb_verify_requests_keys*)
+LB_INDEX_LISTS = 8
+LB_SHUFFLE_MAX = 4194304
+LB_KEYS_DIRECT = 0
+LB_KEYS_SLICE = 1
+LB_KEYS_BITS = 2
+# one lb_set_keys per set: kind, list, a, len, bits_off
+SET_KEYS_DTYPE = np.dtype([("kind", "<u4"), ("list", "<u4"), ("a", "<u4"), ("len", "<u4"), ("bits_off", "<u4")])
 
 # blob KZG proof verification (lb_kzg_*)
 LB_KZG_BLOB_BYTES = 131072
@@ -119,6 +131,16 @@ class _SameMessageBatch(ctypes.Structure):
         ("sig_offsets", ctypes.c_void_p),
         ("messages", ctypes.c_void_p),
         ("seed", ctypes.c_void_p),
+    ]
+
+
+class _KeySource(ctypes.Structure):
+    _fields_ = [
+        ("sets", ctypes.c_void_p),
+        ("key_pool", ctypes.c_void_p),
+        ("n_pool", ctypes.c_uint32),
+        ("bits", ctypes.c_void_p),
+        ("n_bits_bytes", ctypes.c_uint32),
     ]
 
 
@@ -228,6 +250,17 @@ def load_library() -> ctypes.CDLL:
     lib.lb_set_latency_path.argtypes = [vp, u32]
     lib.lb_lp_program_run.argtypes = [vp, u32, vp, ctypes.c_size_t, u32, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
                                       vp]
+    lib.lb_index_list_put.argtypes = [vp, u32, u32, vp]
+    lib.lb_index_list_shuffle.argtypes = [vp, u32, u32, vp, vp, vp]
+    lib.lb_index_list_size.argtypes = [vp, u32, ctypes.POINTER(u32)]
+    lib.lb_index_list_read.argtypes = [vp, u32, u32, u32, vp]
+    lib.lb_verify_requests_keys.argtypes = [vp, ctypes.POINTER(_RequestBatch), ctypes.POINTER(_KeySource), vp, vp, vp,
+                                            ctypes.POINTER(_Stats)]
+    for name in ("lb_verify_requests_keys_async", "lb_verify_requests_keys_priority_async",
+                 "lb_verify_requests_keys_partial_async"):
+        getattr(lib, name).argtypes = [vp, ctypes.POINTER(_RequestBatch), ctypes.POINTER(_KeySource), vp, vp, vp,
+                                       ctypes.POINTER(ctypes.c_uint64)]
+    lib.lb_expand_set_keys.argtypes = [vp, u32, ctypes.POINTER(_KeySource), vp, vp, u32]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name).restype = getattr(lib, name).restype or ctypes.c_int
     _lib = lib
@@ -418,6 +451,111 @@ class Device:
             self._check(rc, "lb_verify_requests_priority_async" if priority else "lb_verify_requests_async")
         pc.ticket = int(t.value)
         return pc
+
+    # -- set keys by descriptor (device-resident index lists) ----------------------
+    @staticmethod
+    def _key_source(set_keys, key_pool=None, bits=None):
+        """(lb_key_source struct, arrays it points into) from a SET_KEYS_DTYPE array (or rows of
+        (kind, list, a, len, bits_off)), the SLICE sets' index pool and the BITS sets' bytes."""
+        sets = np.ascontiguousarray(set_keys, dtype=np.uint32).reshape(-1, 5).view(SET_KEYS_DTYPE).reshape(-1) \
+            if not (isinstance(set_keys, np.ndarray) and set_keys.dtype == SET_KEYS_DTYPE) \
+            else np.ascontiguousarray(set_keys)
+        pool = np.zeros(0, np.uint32) if key_pool is None else np.ascontiguousarray(key_pool, dtype=np.uint32)
+        bits_a = np.zeros(0, np.uint8) if bits is None else _u8(bits)
+        n_pool, n_bits = len(pool), len(bits_a)
+        # (a pointer stays non-NULL for an empty array)
+        sets_p = sets if len(sets) else np.zeros(1, SET_KEYS_DTYPE)
+        pool_p = pool if n_pool else np.zeros(1, np.uint32)
+        bits_p = bits_a if n_bits else np.zeros(1, np.uint8)
+        ks = _KeySource(_ptr(sets_p), _ptr(pool_p), n_pool, _ptr(bits_p), n_bits)
+        return ks, (sets_p, pool_p, bits_p), len(sets)
+
+    def _keys_batch(self, request_offsets, set_keys, key_pool, bits, messages, sig_blob, sig_offsets, seed, batchable):
+        b, keep, n_req, n_sets = self._host_batch(request_offsets, None, None, messages, sig_blob, sig_offsets, seed,
+                                                  batchable)
+        b.pubkeys = None
+        ks, keep_k, n_desc = self._key_source(set_keys, key_pool, bits)
+        if n_desc != n_sets:
+            raise ValueError(f"{n_desc} set descriptors for {n_sets} sets")
+        return b, ks, (keep, keep_k), n_req, n_sets
+
+    def verify_requests_keys(self, request_offsets, set_keys, key_pool, bits, messages, sig_blob, sig_offsets,
+                             seed: bytes, batchable=None) -> VerifyResult:
+        """lb_verify_requests_keys: every set's keys by descriptor (DIRECT index, SLICE of key_pool,
+        BITS over a slice of a device-resident index list) instead of pubkeys or pk_indices."""
+        b, ks, keep, n_req, n_sets = self._keys_batch(request_offsets, set_keys, key_pool, bits, messages, sig_blob,
+                                                      sig_offsets, seed, batchable)
+        valid = np.zeros(max(n_req, 1), np.uint8)
+        err = np.zeros(max(n_req, 1), np.uint8)
+        sst = np.zeros(max(n_sets, 1), np.uint8)
+        st = _Stats()
+        rc = self.lib.lb_verify_requests_keys(self._h, ctypes.byref(b), ctypes.byref(ks), _ptr(valid), _ptr(err),
+                                              _ptr(sst), ctypes.byref(st))
+        self._check(rc, "lb_verify_requests_keys")
+        del keep
+        return VerifyResult(valid[:n_req], err[:n_req], sst[:n_sets], st.device_ms, int(st.batch_retries),
+                            int(st.batch_sigs_success))
+
+    def verify_requests_keys_async(self, request_offsets, set_keys, key_pool, bits, messages, sig_blob, sig_offsets,
+                                   seed: bytes, batchable=None, partial: bool = False,
+                                   priority: bool = False) -> "PendingCall":
+        """The async, priority and two-phase forms of verify_requests_keys; wait_call(), partial_wait(),
+        verify_finish() as for verify_requests_async."""
+        if partial and priority:
+            raise ValueError("a two-phase call cannot take the priority lane")
+        b, ks, keep, n_req, n_sets = self._keys_batch(request_offsets, set_keys, key_pool, bits, messages, sig_blob,
+                                                      sig_offsets, seed, batchable)
+        # (the released two-phase flow re-reads the structs too: they live as long as the call)
+        pc = PendingCall(0, n_req, n_sets, np.zeros(max(n_req, 1), np.uint8), np.zeros(max(n_req, 1), np.uint8),
+                         np.zeros(max(n_sets, 1), np.uint8), (keep, b, ks), partial)
+        name = "lb_verify_requests_keys_" + ("partial_async" if partial else "priority_async" if priority else "async")
+        t = ctypes.c_uint64(0)
+        rc = getattr(self.lib, name)(self._h, ctypes.byref(b), ctypes.byref(ks), _ptr(pc.valid), _ptr(pc.err),
+                                     _ptr(pc.sst), ctypes.byref(t))
+        self._check(rc, name)
+        pc.ticket = int(t.value)
+        return pc
+
+    def expand_set_keys(self, set_keys, key_pool=None, bits=None, max_indices: Optional[int] = None):
+        """lb_expand_set_keys: (pk_offsets[n_sets + 1], indices) the descriptors expand to."""
+        ks, keep, n_sets = self._key_source(set_keys, key_pool, bits)
+        if max_indices is None:
+            max_indices = int(sum(1 if int(k) == LB_KEYS_DIRECT else int(ln)
+                                  for k, ln in zip(keep[0]["kind"][:n_sets], keep[0]["len"][:n_sets])))
+        pk_off = np.zeros(n_sets + 1, np.uint32)
+        idx = np.zeros(max(max_indices, 1), np.uint32)
+        rc = self.lib.lb_expand_set_keys(self._h, n_sets, ctypes.byref(ks), _ptr(pk_off), _ptr(idx), max_indices)
+        self._check(rc, "lb_expand_set_keys")
+        return pk_off, idx[:int(pk_off[-1])]
+
+    def index_list_put(self, list_id: int, indices) -> None:
+        """lb_index_list_put: store validator indices as list `list_id` (empty: unload the id)."""
+        a = np.ascontiguousarray(indices, dtype=np.uint32)
+        buf = a if len(a) else np.zeros(1, np.uint32)
+        self._check(self.lib.lb_index_list_put(self._h, list_id, len(a), _ptr(buf)), "lb_index_list_put")
+
+    def index_list_shuffle(self, list_id: int, active_indices, seed: bytes, want_output: bool = True):
+        """lb_index_list_shuffle: store unshuffleList(active_indices, seed) as list `list_id`;
+        returns the shuffling (uint32 array) unless want_output is False."""
+        a = np.ascontiguousarray(active_indices, dtype=np.uint32)
+        buf = a if len(a) else np.zeros(1, np.uint32)
+        seed_a = _u8(seed)
+        if len(seed_a) != 32:
+            raise ValueError("seed must be 32 bytes")
+        out = np.zeros(max(len(a), 1), np.uint32) if want_output else None
+        rc = self.lib.lb_index_list_shuffle(self._h, list_id, len(a), _ptr(buf), _ptr(seed_a), _ptr(out))
+        self._check(rc, "lb_index_list_shuffle")
+        return None if out is None else out[:len(a)]
+
+    def index_list_size(self, list_id: int) -> int:
+        n = ctypes.c_uint32(0)
+        self._check(self.lib.lb_index_list_size(self._h, list_id, ctypes.byref(n)), "lb_index_list_size")
+        return int(n.value)
+
+    def index_list_read(self, list_id: int, first: int, n: int) -> np.ndarray:
+        out = np.zeros(max(n, 1), np.uint32)
+        self._check(self.lib.lb_index_list_read(self._h, list_id, first, n, _ptr(out)), "lb_index_list_read")
+        return out[:n]
 
     def wait_call(self, pc: "PendingCall") -> VerifyResult:
         st = _Stats()

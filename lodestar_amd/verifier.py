@@ -39,7 +39,7 @@ from typing import Callable, Deque, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import metrics as M
-from .native import (LB_PK_ROW_FLAG, PendingSameMessage, LB_REQ_BAD_PUBKEY, LB_REQ_EMPTY_AGGREGATE, BadPubkeyError, Device, EmptyAggregateError,
+from .native import (LB_KEYS_BITS, LB_KEYS_DIRECT, LB_KEYS_SLICE, LB_PK_ROW_FLAG, PendingSameMessage, LB_REQ_BAD_PUBKEY, LB_REQ_EMPTY_AGGREGATE, BadPubkeyError, Device, EmptyAggregateError,
                      pack_blobs)
 
 MAX_SIGNATURE_SETS_PER_JOB = 128      # index.ts:57
@@ -52,6 +52,9 @@ BATCHABLE_MIN_PER_CHUNK = 16          # worker.ts:17
 class SignatureSetType(str, enum.Enum):
     single = "single"
     aggregate = "aggregate"
+    # an aggregate whose keys are the set bits over a slice of a device-resident index list
+    # (bits_set): the attestation as it arrived, a committee plus its aggregation bits
+    bits = "bits"
 
 
 @dataclass
@@ -80,6 +83,11 @@ class SignatureSet:
     signature: bytes
     pubkey: Optional[PublicKey] = None          # single
     pubkeys: Optional[List[PublicKey]] = None   # aggregate
+    # bits: keys = list[start + j] for every set bit j < length (bit j = bits[j // 8] >> (j % 8) & 1)
+    list_id: int = 0
+    start: int = 0
+    length: int = 0
+    bits: bytes = b""
 
 
 def single_set(pubkey: PublicKey, signing_root: bytes, signature: bytes) -> SignatureSet:
@@ -88,6 +96,41 @@ def single_set(pubkey: PublicKey, signing_root: bytes, signature: bytes) -> Sign
 
 def aggregate_set(pubkeys: Sequence[PublicKey], signing_root: bytes, signature: bytes) -> SignatureSet:
     return SignatureSet(SignatureSetType.aggregate, signing_root, signature, pubkeys=list(pubkeys))
+
+
+def bits_set(list_id: int, start: int, length: int, bits: bytes, signing_root: bytes,
+             signature: bytes) -> SignatureSet:
+    """An aggregate set over a committee: slice [start, start + length) of index list `list_id`
+    (DeviceBackend.sync_shuffling / put_index_list) and the participation bits, in SSZ bit order
+    with any delimiter bit stripped -- what getAttestingIndices' intersectValues walks on the host
+    (state-transition/src/cache/epochCache.ts:684-685) goes to the GPU as it arrived."""
+    bits = bytes(bits)
+    if length < 0 or start < 0 or len(bits) < (length + 7) // 8:
+        raise ValueError("bits_set: %d bits need %d bytes" % (length, (length + 7) // 8))
+    return SignatureSet(SignatureSetType.bits, signing_root, signature, list_id=int(list_id), start=int(start),
+                        length=int(length), bits=bits[:(length + 7) // 8])
+
+
+def pack_set_keys(sets: Sequence[SignatureSet]):
+    """Descriptors (lb_set_keys rows: kind, list, a, len, bits_off), the SLICE sets' index pool
+    and the BITS sets' bytes for sets whose every key is a validator index or a bits set; None
+    when a key has bytes only (the package then goes in today's form)."""
+    rows, pool, bits = [], [], bytearray()
+    for s in sets:
+        if s.type == SignatureSetType.bits:
+            rows.append((LB_KEYS_BITS, s.list_id, s.start, s.length, len(bits)))
+            bits += s.bits
+            continue
+        keys = [s.pubkey] if s.type == SignatureSetType.single else (s.pubkeys or [])
+        if any(k.index is None for k in keys):
+            return None
+        if s.type == SignatureSetType.single:
+            rows.append((LB_KEYS_DIRECT, 0, keys[0].index, 0, 0))
+        else:
+            rows.append((LB_KEYS_SLICE, 0, len(pool), len(keys), 0))
+            pool.extend(k.index for k in keys)
+    return (np.array(rows, np.uint32).reshape(-1, 5), np.array(pool, np.uint32),
+            np.frombuffer(bytes(bits), np.uint8))
 
 
 @dataclass
@@ -298,11 +341,24 @@ class DeviceBackend:
                 fut.set_exception(e)
         self.dev.close()
 
+    def _expand_bits_set(self, s: SignatureSet) -> List[PublicKey]:
+        """A bits set's keys on the host, from the list as the device holds it (a package that
+        cannot go as descriptors: one of its keys has bytes only)"""
+        ix = self.dev.index_list_read(s.list_id, s.start, s.length)
+        return [PublicKey(index=int(ix[j])) for j in range(s.length) if (s.bits[j >> 3] >> (j & 7)) & 1]
+
     def _submit_requests(self, requests: List[List[SignatureSet]], partial: bool):
+        # a package with bits sets whose other keys are all validator indices goes as set
+        # descriptors (lb_verify_requests_keys*): the GPU expands bits to indices
+        if any(s.type == SignatureSetType.bits for req in requests for s in req):
+            packed = pack_set_keys([s for req in requests for s in req])
+            if packed is not None:
+                return self._submit_keys(requests, packed, partial)
         keys_all, pk_off, msgs, sigs, req_off = [], [0], [], [], [0]
         for req in requests:
             for s in req:
-                keys = [s.pubkey] if s.type == SignatureSetType.single else (s.pubkeys or [])
+                keys = [s.pubkey] if s.type == SignatureSetType.single else \
+                    self._expand_bits_set(s) if s.type == SignatureSetType.bits else (s.pubkeys or [])
                 keys_all.extend(keys)
                 pk_off.append(len(keys_all))
                 if len(s.signing_root) != 32:
@@ -334,6 +390,25 @@ class DeviceBackend:
         pc = self.dev.verify_requests_async(np.array(req_off, np.uint32), pks, np.array(pk_off, np.uint32),
                                             np.frombuffer(b"".join(msgs) or b"\0", np.uint8), blob, offs,
                                             self.seed_source(), pk_indices=idx, partial=partial)
+
+        def post(res, cs):
+            return [bool(v) for v in res.valid], [int(e) for e in res.errors], cs
+        return pc, post
+
+    def _submit_keys(self, requests, packed, partial: bool):
+        set_keys, pool, bits = packed
+        msgs, sigs, req_off = [], [], [0]
+        for req in requests:
+            for s in req:
+                if len(s.signing_root) != 32:
+                    raise ValueError("signing_root must be 32 bytes")
+                msgs.append(bytes(s.signing_root))
+                sigs.append(bytes(s.signature))
+            req_off.append(len(msgs))
+        blob, offs = pack_blobs(sigs)
+        pc = self.dev.verify_requests_keys_async(np.array(req_off, np.uint32), set_keys, pool, bits,
+                                                 np.frombuffer(b"".join(msgs) or b"\0", np.uint8), blob, offs,
+                                                 self.seed_source(), partial=partial)
 
         def post(res, cs):
             return [bool(v) for v in res.valid], [int(e) for e in res.errors], cs
@@ -428,6 +503,16 @@ class DeviceBackend:
         compressed, as the state holds them) to the device table; returns its size."""
         return self._put("call", lambda cs: self.dev.pubkey_table_append(list(pubkeys))).result()
 
+    def sync_shuffling(self, list_id: int, active_indices, seed: bytes) -> np.ndarray:
+        """computeEpochShuffling's unshuffleList (util/epochShuffling.ts:62-101) on the GPU: index
+        list `list_id` becomes the epoch's shuffling, which is also returned (uint32 array) for
+        the host's EpochShuffling; committees are slices of it (bits_set)."""
+        return self._put("call", lambda cs: self.dev.index_list_shuffle(list_id, active_indices, seed)).result()
+
+    def put_index_list(self, list_id: int, indices) -> None:
+        """Store validator indices as given (a sync committee's) as index list `list_id`."""
+        return self._put("call", lambda cs: self.dev.index_list_put(list_id, indices)).result()
+
     def close(self) -> None:
         """Finish every queued and in-flight call, then release the device
         (from the submission thread, after its last call -- never under one)."""
@@ -486,6 +571,15 @@ class BlsGpuVerifier:
         if len(set(sizes)) != 1:
             raise RuntimeError(f"pubkey tables out of sync across devices: {sizes}")
         return sizes[0]
+
+    def sync_shuffling(self, list_id: int, active_indices, seed: bytes) -> np.ndarray:
+        """The epoch's shuffling computed on, and kept by, every GPU as index list `list_id`."""
+        outs = [b.sync_shuffling(list_id, active_indices, seed) for b in self.backends]
+        return outs[0]
+
+    def put_index_list(self, list_id: int, indices) -> None:
+        for b in self.backends:
+            b.put_index_list(list_id, indices)
 
     # ---- IBlsVerifier --------------------------------------------------------------
     def can_accept_work(self) -> bool:
