@@ -18,6 +18,7 @@ HEADERS = ["bls_kernels.h", "bls_limits.h", "bls_inv.h", "bls_field.h", "bls_fp_
 # headers / generated files only some units depend on (a regenerated program blob must
 # not rebuild every kernel unit)
 UNIT_DEPS = {"k_lp.hip": ["bls_coop.h", "bls_lp.h", "bls_lp_progs.h"], "lp_blob.hip": ["lp_programs.bin"],
+             "k_steps.hip": ["bls_steps_walk.h"],
              "k_kzg.hip": ["bls_fr.h", "bls_kzg.h"], "k_kzg_msm.hip": ["bls_fr.h", "bls_kzg.h"],
              "bls_host.hip": ["bls_lp.h", "bls_lp_progs.h", "bls_fr.h", "bls_kzg.h", "bls_plan.h", "bls_ctx_plan.h",
                               "bls_carve.h"]}

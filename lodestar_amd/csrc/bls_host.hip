@@ -21,7 +21,8 @@
 //   k_msm_*                per call    : S_all = sum r_i sig_i over the good requests, one
 //                                        bucket MSM (k_msm.hip); small calls: per-set ladders
 //                                        (k_scalar_sig + k_sum_tree), also the S_k of the tails
-//   k_step_acc             per set     : step-major lanes over the stored lines (k_steps.hip)
+//   k_step_acc             per set     : step-major lanes over the stored lines (k_steps.hip;
+//                                        from 8,192 sets k_line_pairs multiplies their line pairs first)
 //   k_level_part/_wc       per call    : the 63 level products of the merged check
 //   k_lp_mtail             per call    : merged check as a round program: S_all from the MSM's
 //                                        bit sums, Miller(-g1, S_all), Horner chain, final exp
@@ -671,6 +672,10 @@ static decltype(&k_lines_rows<1>) lines_rows_kernel(const PipePlan& p) {
   return p.lines_W == 1 ? k_lines_rows<1> : k_lines_rows<2>;
 }
 static decltype(&k_step_acc<0, 1>) step_acc_kernel(const PipePlan& p) {
+  if (p.pair_pre) {  // (never with step_M == 2: plan_pipeline)
+    if (p.step_M == 1) return k_step_acc<1, 1, true>;
+    return p.step_W == 2 ? k_step_acc<0, 2, true> : k_step_acc<0, 1, true>;
+  }
   if (p.step_M == 1) return k_step_acc<1, 1>;
   if (p.step_M == 2) return p.step_W == 2 ? k_step_acc<2, 2> : k_step_acc<2, 1>;
   return p.step_W == 2 ? k_step_acc<0, 2> : k_step_acc<0, 1>;
@@ -869,6 +874,9 @@ static int enqueue_acc_steps(lb_ctx* ctx, Slot& sl, const PipePlan& p, const Pip
   // (steps + merged: the merged pair's lines come from a one-lane kernel before the
   // accumulation; as an extra workgroup of k_step_acc they measured 4.8 -> 8.2 ms: the
   // 1,025th wave waits for a SIMD of the 1,024 set waves, then runs the 3.4 ms line chain)
+  if (p.pair_pre)  // the pairs' line products first, in place, at two waves per SIMD (k_steps.hip)
+    LB_STAGE("step_acc", 0, k_line_pairs, blocks_for(n_sets * lsplit * (LB_MILLER_LINES / lsplit / 2u)), TPB, n_sets,
+             n_pairs, b.rows, b.req_off, b.lines);
   LB_STAGE("step_acc", 0, step_acc_kernel(p), blocks_for(n_sets * lsplit), TPB, n_sets, n_pairs, b.rows, b.req_off,
            (const uint32_t*)b.lines, b.G);
   if (!p.merged) {
@@ -1362,7 +1370,9 @@ static std::string g_create_err = "null context";
 size_t scratch_per_queue(int device, DeviceFacts* out_facts) {
   const void* kernels[] = {(const void*)k_miller_acc<16>, (const void*)k_miller_acc<32>,
                            (const void*)k_miller_acc<64>, (const void*)k_step_acc<0, 1>,
-                           (const void*)k_step_acc<0, 2>, (const void*)k_step_acc<1, 1>, (const void*)k_step_acc<2, 1>, (const void*)k_step_acc<2, 2>, (const void*)k_lines<1>,
+                           (const void*)k_step_acc<0, 2>, (const void*)k_step_acc<1, 1>, (const void*)k_step_acc<2, 1>, (const void*)k_step_acc<2, 2>,
+                           (const void*)k_step_acc<0, 1, true>, (const void*)k_step_acc<0, 2, true>,
+                           (const void*)k_step_acc<1, 1, true>, (const void*)k_line_pairs, (const void*)k_lines<1>,
                            (const void*)k_lines<2>, (const void*)k_lines_rows<1>, (const void*)k_lines_rows<2>,
                            (const void*)k_pair_wc, (const void*)k_miller_sets,
                            (const void*)k_hash_half, (const void*)k_hash_finish, (const void*)k_final,

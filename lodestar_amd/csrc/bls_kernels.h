@@ -305,11 +305,14 @@ __global__ void __launch_bounds__(TPB) k_req_status(uint32_t n_req, const uint32
                                                     const uint8_t* __restrict__ sig_status,
                                                     const uint8_t* __restrict__ pk_status,
                                                     uint8_t* __restrict__ req_bad, uint8_t* __restrict__ req_err);
-template <int MODE, int WAVES>
+// (PRE: the line pairs' products stored in place by k_line_pairs, run before it)
+template <int MODE, int WAVES, bool PRE = false>
 __global__ void __launch_bounds__(TPB, WAVES) k_step_acc(uint32_t n_sets, uint32_t n_pairs, Rows R,
                                                             const uint32_t* __restrict__ req_off,
                                                             const uint32_t* __restrict__ lines,
                                                             uint32_t* __restrict__ G);
+__global__ void __launch_bounds__(TPB, 2) k_line_pairs(uint32_t n_sets, uint32_t n_pairs, Rows R,
+                                                       const uint32_t* __restrict__ req_off, uint32_t* lines);
 __global__ void __launch_bounds__(256, 1) k_level_prod(uint32_t n_req, uint32_t n_sets, uint32_t n_pairs,
                                                        uint32_t s_pair, Rows R, const uint32_t* __restrict__ req_off,
                                                        const uint32_t* __restrict__ G,

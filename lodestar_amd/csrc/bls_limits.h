@@ -37,6 +37,14 @@
 #define LB_MTAIL_NIN (12 * LB_MTAIL_LEVELS + 6 * LB_MSM_POS)  // mtail inputs: the 63 level products, the MSM's
                                                               // 33 bit sums
 
+// Steps calls of at least LB_PAIR_PRE_MIN_SETS sets whose lines k_lines_rows stores multiply their
+// line pairs in k_line_pairs ahead of k_step_acc (k_steps.hip): above the LB_LP_LINES_MAX band of
+// the round-program lines.  LB_PAIR_PRE=0 at compile time removes the rule (the A/B build).
+#ifndef LB_PAIR_PRE
+#define LB_PAIR_PRE 1
+#endif
+#define LB_PAIR_PRE_MIN_SETS 8192
+
 namespace lb {
 // the 68 lines of one pair (63 doubling + 5 addition steps, loop order): bls_pairing.h
 static constexpr int LB_MILLER_LINES = 68;

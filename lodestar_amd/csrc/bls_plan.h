@@ -326,6 +326,10 @@ struct PipePlan {
   bool miller_wave = false, miller_sets = false;
   int lines_W = 1;              // k_lines<W> / k_lines_rows<W>
   int step_M = 1, step_W = 1;   // k_step_acc<M, W>
+  // the products of a lane's line pairs (line_mul_line: 6 of the 23 Fp2 products of a pair, which
+  // touch no accumulator) in k_line_pairs, a two-wave kernel that shares SIMDs with other calls'
+  // waves, ahead of the one-wave k_step_acc<M, W, true>; lone and shared calls alike
+  bool pair_pre = false;
   int acc_lpr = 64;             // k_miller_acc<L>
 };
 
@@ -389,6 +393,7 @@ inline PipePlan plan_pipeline(const PipeConfig& c, const PipeShape& s) {
   p.decode = (!n_sets || s.presigned) ? DECODE_NONE : p.dec_lp ? DECODE_LP : DECODE_PLAIN;
   p.step_M = c.step_mode == 1 ? 1 : c.step_mode == 2 ? 2 : 0;
   p.step_W = c.step_mode == 1 ? 1 : c.step_waves == 2 ? 2 : 1;
+  p.pair_pre = LB_PAIR_PRE && p.steps && p.step_M != 2 && p.lines == LINES_ROWS && n_sets >= LB_PAIR_PRE_MIN_SETS;
   p.acc_lpr = c.acc_lpr == 16 ? 16 : c.acc_lpr == 32 ? 32 : 64;
   return p;
 }

@@ -23,6 +23,7 @@
 // every lane reads line (j, i) of its request at the same moment and the SoA
 // loads (word w of line j of slot q at lines[(j*72 + w)*n_pairs + q]) coalesce.
 #include "bls_kernels.h"
+#include "bls_steps_walk.h"
 #include "bls_wc12.h"
 
 namespace lb {
@@ -274,28 +275,49 @@ struct AccLds {
   LB_DEV void get(fp12& v) const { v = *A; }
 };
 
-template <bool PAIRED, class Acc>
+// words 0..47 of line j of slot q: the (y1, y2) of a pair's product stored by k_line_pairs
+LB_DEV void line_get_y(const uint32_t* __restrict__ lines, size_t n_pairs, size_t q, int j, fp2& y1, fp2& y2) {
+  const uint32_t* p = lines + (size_t)j * 72 * n_pairs + q;
+  fp* c[4] = {&y1.c0, &y1.c1, &y2.c0, &y2.c1};
+#pragma unroll
+  for (int e = 0; e < 4; e++)
+#pragma unroll
+    for (int w = 0; w < 12; w++) c[e]->l[w] = p[(size_t)(12 * e + w) * n_pairs];
+}
+
+// PRE: k_line_pairs has run over `lines` -- a pair's product (x, y1, y2) is read where it left
+// it (x over the first line, y1 and y2 over words 0..47 of the second) instead of multiplying
+// the two lines here.  The items are those of bls_steps_walk.h, which k_line_pairs walks too.
+template <bool PAIRED, bool PRE, class Acc>
 LB_DEV void step_lines(Acc& acc, const uint32_t* __restrict__ lines, uint32_t n_pairs, const Rows& R, uint32_t r,
                        uint32_t n, uint32_t t0, uint32_t cnt) {
-  uint32_t j = t0 / n, i = t0 - j * n;
-  int lvl = c_steps.lvl[j];
+  StepWalk walk(n, t0, cnt, PAIRED);
+  int lvl = c_steps.lvl[walk.j];
   bool have = false;
   fp2 l0, l1, l4;
 #pragma unroll 1
-  for (uint32_t c = 0; c < cnt;) {
+  while (!walk.done()) {
+    const StepItem it = walk.next();
+    const uint32_t j = it.j, i = it.i;
     const int lj = c_steps.lvl[j];
     if (lj != lvl) {  // one doubling step further: one squaring
       if (have) acc.sqr();
       lvl = lj;
     }
     const uint32_t qa = R.rowoff[i] + r;
-    if (PAIRED && i + 1 < n && c + 1 < cnt) {  // two lines of the same step
+    if (PAIRED && it.paired) {  // two lines of the same step
       const uint32_t qb = R.rowoff[i + 1] + r;
-      fp2 m0, m1, m4, y1, y2;
+      fp2 y1, y2;
       fp6 x;
-      line_get(lines, n_pairs, qa, (int)j, l0, l1, l4);
-      line_get(lines, n_pairs, qb, (int)j, m0, m1, m4);
-      line_mul_line(x, y1, y2, l0, l1, l4, m0, m1, m4);
+      if constexpr (PRE) {
+        line_get(lines, n_pairs, qa, (int)j, x.c0, x.c1, x.c2);
+        line_get_y(lines, n_pairs, qb, (int)j, y1, y2);
+      } else {
+        fp2 m0, m1, m4;
+        line_get(lines, n_pairs, qa, (int)j, l0, l1, l4);
+        line_get(lines, n_pairs, qb, (int)j, m0, m1, m4);
+        line_mul_line(x, y1, y2, l0, l1, l4, m0, m1, m4);
+      }
       if (have) {
         acc.mul_sparse2(x, y1, y2);
       } else {
@@ -307,8 +329,6 @@ LB_DEV void step_lines(Acc& acc, const uint32_t* __restrict__ lines, uint32_t n_
         acc.set(v);
         have = true;
       }
-      i += 2;
-      c += 2;
     } else {
       line_get(lines, n_pairs, qa, (int)j, l0, l1, l4);
       if (have) {
@@ -323,14 +343,119 @@ LB_DEV void step_lines(Acc& acc, const uint32_t* __restrict__ lines, uint32_t n_
         acc.set(v);
         have = true;
       }
-      i += 1;
-      c += 1;
-    }
-    if (i >= n) {
-      i -= n;
-      j++;
     }
   }
+}
+
+// The line pairs of every lane multiplied ahead of k_step_acc<M, W, true> (PipePlan::pair_pre).
+// Of the 23 Fp2 products a pair costs, line_mul_line's 6 read two stored lines and nothing of
+// the accumulator; k_step_acc holds a whole SIMD's registers (one wave per SIMD), this kernel
+// runs at two waves per SIMD and shares them with other calls' waves.
+// One thread per (lane part t, pair index u < L / 2), u-major: consecutive threads are
+// consecutive slots, so loads and stores coalesce as k_step_acc's do.  The thread finds the
+// u-th pair of its lane by the walk k_step_acc takes (bls_steps_walk.h) and writes the product
+// in place: x (72 words) over line (j, qa), y1 and y2 over words 0..47 of line (j, qb).
+// Invariant: every line of a set slot belongs to exactly one item of one lane, and after the
+// lines are stored only k_step_acc reads set-slot lines, so the records displace nothing that
+// is read again.  Words 48..71 of (j, qb), single lines, and the slots >= n_sets (the S_k pairs
+// and the merged pair) are not written.
+//
+// Streaming form: the six products one after another, operands read again from memory for
+// each, an output stored when complete, so that at most three Fp2 values are held across a
+// product (the whole pair product in registers spills).  The stores go where the lines they
+// displace are dead: l4, m4 after the three products that use them, and so on; (j, qa)'s third
+// coefficient holds a partial sum in between.  The sums are regrouped against line_mul_line
+// ((k - p44) - p00 for (k - p00) - p44): field values are kept fully reduced (bls_field.h), so
+// the stored words are the same.
+// (the fence names the pointer so that the loads behind it are not hoisted above it)
+#define LB_PAIR_FENCE(p) asm volatile("" : "+v"(p)::"memory")
+#define LB_PAIR_FENCES(a, b) \
+  do {                       \
+    LB_PAIR_FENCE(a);        \
+    LB_PAIR_FENCE(b);        \
+  } while (0)
+LB_DEV void pair_ld(fp2& v, const uint32_t* p, size_t n_pairs, int e) {
+  p += (size_t)24 * e * n_pairs;
+#pragma unroll
+  for (int w = 0; w < 12; w++) {
+    v.c0.l[w] = p[(size_t)w * n_pairs];
+    v.c1.l[w] = p[(size_t)(12 + w) * n_pairs];
+  }
+}
+LB_DEV void pair_st(uint32_t* p, size_t n_pairs, int e, const fp2& v) {
+  p += (size_t)24 * e * n_pairs;
+#pragma unroll
+  for (int w = 0; w < 12; w++) {
+    p[(size_t)w * n_pairs] = v.c0.l[w];
+    p[(size_t)(12 + w) * n_pairs] = v.c1.l[w];
+  }
+}
+// (a e_a + a e_b)(b e_a + b e_b): the Karatsuba cross product of coefficients e_a, e_b
+LB_DEV void pair_cross(fp2& k, uint32_t*& A, uint32_t*& B, size_t n_pairs, int ea, int eb) {
+  fp2 s, t;
+  pair_ld(s, A, n_pairs, ea);
+  pair_ld(t, A, n_pairs, eb);
+  fp2_add(s, s, t);
+  LB_PAIR_FENCES(A, B);  // (the second line's loads after the first sum, the product after both)
+  pair_ld(t, B, n_pairs, ea);
+  pair_ld(k, B, n_pairs, eb);
+  fp2_add(t, t, k);
+  LB_PAIR_FENCES(A, B);
+  fp2_mul(k, s, t);
+}
+LB_DEV void pair_prod(fp2& p, const uint32_t* A, const uint32_t* B, size_t n_pairs, int e) {
+  fp2 a, b;
+  pair_ld(a, A, n_pairs, e);
+  pair_ld(b, B, n_pairs, e);
+  fp2_mul(p, a, b);
+}
+__global__ void __launch_bounds__(TPB, 2) k_line_pairs(uint32_t n_sets, uint32_t n_pairs, Rows R,
+                                                       const uint32_t* __restrict__ req_off, uint32_t* lines) {
+  const uint32_t L = (uint32_t)LB_MILLER_LINES / R.split, parts = n_sets * R.split;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t u = g / parts, t = g - u * parts;
+  if (u >= L / 2) return;
+  const uint32_t q = t / R.split, h = t - q * R.split;
+  uint32_t l, r;
+  slot_row(R, q, l, r);
+  const uint32_t k = R.inv[r];
+  const uint32_t n = req_off[k + 1] - req_off[k];
+  uint32_t j, i;
+  if (!step_walk_pair(n, (uint32_t)LB_MILLER_LINES * l + L * h, L, u, j, i)) return;
+  uint32_t* A = lines + (size_t)j * 72 * n_pairs + (R.rowoff[i] + r);      // l0, l1, l4 -> x0, x1, x2
+  uint32_t* B = lines + (size_t)j * 72 * n_pairs + (R.rowoff[i + 1] + r);  // m0, m1, m4 -> y1, y2, m4
+  fp2 p44, p, v, w;
+  pair_prod(p44, A, B, n_pairs, 2);
+  LB_PAIR_FENCES(A, B);
+  pair_cross(v, A, B, n_pairs, 1, 2);
+  fp2_sub(v, v, p44);  // y2 + p11
+  LB_PAIR_FENCES(A, B);
+  pair_cross(w, A, B, n_pairs, 0, 2);
+  fp2_sub(w, w, p44);  // y1 + p00; l4 and m4 are done with
+  pair_st(A, n_pairs, 2, v);
+  LB_PAIR_FENCES(A, B);
+  pair_prod(p, A, B, n_pairs, 1);  // p11
+  LB_PAIR_FENCES(A, B);
+  pair_cross(v, A, B, n_pairs, 0, 1);
+  fp2_sub(v, v, p);  // x1 + p00; l1 and m1 are done with
+  LB_PAIR_FENCES(A, B);
+  {
+    fp2 y2;
+    pair_ld(y2, A, n_pairs, 2);
+    fp2_sub(y2, y2, p);
+    pair_st(B, n_pairs, 1, y2);
+  }
+  pair_st(A, n_pairs, 2, p);  // x2 = p11
+  LB_PAIR_FENCES(A, B);
+  pair_prod(p, A, B, n_pairs, 0);  // p00
+  fp2_sub(v, v, p);
+  pair_st(A, n_pairs, 1, v);  // x1 = l0 m1 + l1 m0
+  LB_PAIR_FENCES(A, B);
+  fp2_sub(w, w, p);
+  pair_st(B, n_pairs, 0, w);  // y1 = l0 m4 + l4 m0
+  fp2_mul_xi(v, p44);
+  fp2_add(v, v, p);
+  pair_st(A, n_pairs, 0, v);  // x0 = p00 + xi p44
 }
 
 // MODE 0: accumulator in registers, two lines of a step through the sparse x sparse
@@ -340,7 +465,8 @@ LB_DEV void step_lines(Acc& acc, const uint32_t* __restrict__ lines, uint32_t n_
 // WAVES: the occupancy target (1: 512 registers, the accumulator in registers; 2: 256,
 // spilling, but a SIMD interleaves two waves' VALU issue: one wave alone issues a VALU
 // instruction every 4 cycles, two every 2 (MI355X_MICROARCH.md); LB_STEP_WAVES=2).
-template <int MODE, int WAVES>
+// PRE (MODE 0 and 1): the pairs' line products come from k_line_pairs (step_lines).
+template <int MODE, int WAVES, bool PRE>
 __global__ void __launch_bounds__(TPB, WAVES) k_step_acc(uint32_t n_sets, uint32_t n_pairs, Rows R,
                                                             const uint32_t* __restrict__ req_off,
                                                             const uint32_t* __restrict__ lines,
@@ -358,11 +484,12 @@ __global__ void __launch_bounds__(TPB, WAVES) k_step_acc(uint32_t n_sets, uint32
   fp12 out;
   if constexpr (MODE == 1) {
     AccLds acc{&sacc[threadIdx.x].v};
-    step_lines<true>(acc, lines, n_pairs, R, r, n, t0, L);
+    step_lines<true, PRE>(acc, lines, n_pairs, R, r, n, t0, L);
     acc.get(out);
   } else {
+    static_assert(MODE == 0 || !PRE, "one line at a time has no pairs");
     AccReg acc;
-    step_lines<MODE == 0>(acc, lines, n_pairs, R, r, n, t0, L);
+    step_lines<MODE == 0, PRE>(acc, lines, n_pairs, R, r, n, t0, L);
     acc.get(out);
   }
   g_put(G, n_sets * R.split, t, out);
@@ -648,14 +775,17 @@ __global__ void __launch_bounds__(TPB, LB_W_TAIL) k_req_join(uint32_t n_req, uin
   if (threadIdx.x < 12) (&F[k].c0.c0.c0)[threadIdx.x] = S.slot[WC_ACC][threadIdx.x];
 }
 
-#define LB_INST_STEP(M, W)                                                                                      \
-  template __global__ void k_step_acc<M, W>(uint32_t, uint32_t, Rows, const uint32_t* __restrict__,               \
-                                            const uint32_t* __restrict__, uint32_t* __restrict__);
-LB_INST_STEP(0, 1)
-LB_INST_STEP(1, 1)
-LB_INST_STEP(2, 1)
-LB_INST_STEP(0, 2)
-LB_INST_STEP(2, 2)
+#define LB_INST_STEP(M, W, PRE)                                                                                 \
+  template __global__ void k_step_acc<M, W, PRE>(uint32_t, uint32_t, Rows, const uint32_t* __restrict__,          \
+                                                 const uint32_t* __restrict__, uint32_t* __restrict__);
+LB_INST_STEP(0, 1, false)
+LB_INST_STEP(1, 1, false)
+LB_INST_STEP(2, 1, false)
+LB_INST_STEP(0, 2, false)
+LB_INST_STEP(2, 2, false)
+LB_INST_STEP(0, 1, true)
+LB_INST_STEP(1, 1, true)
+LB_INST_STEP(0, 2, true)
 #define LB_INST_LINES_ROWS(W)                                                                                    \
   template __global__ void k_lines_rows<W>(uint32_t, uint32_t, Rows, const uint32_t* __restrict__,                \
                                            const g1j* __restrict__, g2j* __restrict__, uint32_t* __restrict__);
