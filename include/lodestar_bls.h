@@ -519,6 +519,77 @@ int lb_index_list_size(const lb_ctx* ctx, uint32_t list, uint32_t* out_n);
 /* Entries [first, first + n) of the list. */
 int lb_index_list_read(lb_ctx* ctx, uint32_t list, uint32_t first, uint32_t n, uint32_t* out);
 
+/* ---- balance table and balance-weighted sampling: proposers, the sync committee ----------
+ * The two functions the reference marks SLOW CODE in state-transition/src/util/seed.ts:
+ * computeProposers / computeProposerIndex (seed.ts:22-80) and getNextSyncCommitteeIndices
+ * (seed.ts:92-126), with the aggregatePubkey getNextSyncCommittee adds
+ * (util/syncCommittee.ts:21-38).  Both are the spec's rejection sampling over
+ * compute_shuffled_index, weighted by effective balance.
+ *
+ * For one seed s (32 bytes), active indices A[0..n), increments table inc[], max_inc, count
+ * and max_candidates:
+ *
+ *   i = 0, 1, 2, ... while found < count and i < max_candidates:
+ *     cand = A[ compute_shuffled_index(i mod n, n, s) ]   (spec, LB_SHUFFLE_ROUNDS rounds: the
+ *                                                          permutation lb_index_list_shuffle applies)
+ *     rand = SHA256( s || LE64(i div 32) )[ i mod 32 ]
+ *     accepted iff inc[cand] * 255 >= max_inc * rand       (so inc 0 is accepted when rand == 0,
+ *                                                          as in the reference)
+ *     accepted -> out[found++] = cand
+ *
+ *   - out_found[s] is the number accepted.
+ *   - out_tried[s] is (the i of the last accepted candidate) + 1 when found == count, else
+ *     max_candidates.
+ *   - Unfilled places of out hold LB_SAMPLE_NONE (0xFFFFFFFF); the reference's
+ *     computeProposerIndex returns -1 there.
+ *   - Duplicates are kept.  With n < count the walk wraps.
+ *   - computeProposers is 32 seeds with count = 1, max_candidates = n and max_inc = 32.
+ *   - getNextSyncCommitteeIndices is one seed with count = 512.
+ * The reference loops forever if no candidate is ever accepted; here max_candidates bounds the
+ * walk.  The candidates are examined in passes (the first of LB_SAMPLE_FIRST_PASS(count), each
+ * later one twice the last up to LB_SAMPLE_PASS_MAX); no result depends on the pass size.
+ *
+ * The balance table is the reference's EffectiveBalanceIncrements, a Uint8Array indexed by
+ * validator index (cache/effectiveBalanceIncrements.ts:8), kept beside the pubkey table.  A
+ * lb_create_lane context has a table of its own, as it has lists of its own. */
+#define LB_SAMPLE_MAX_SEEDS 64u
+#define LB_SAMPLE_MAX_COUNT 2048u
+#define LB_SAMPLE_MAX_CANDIDATES 4194304u
+#define LB_SAMPLE_NONE 0xFFFFFFFFu
+#define LB_NO_LIST 0xFFFFFFFFu
+#define LB_SAMPLE_FIRST_PASS(count) ((count) == 1u ? 64u : (2u * (count) + 63u) / 64u * 64u)
+#define LB_SAMPLE_PASS_MAX 65536u
+/* Overwrite or append increments [first, first + n) of the table.  first > size ->
+ * LB_ERR_INVALID_ARGUMENT, nothing changed.  Waits for calls in flight. */
+int lb_balance_table_put(lb_ctx* ctx, uint32_t first, uint32_t n, const uint8_t* increments);
+/* Number of validators in the balance table. */
+int lb_balance_table_size(const lb_ctx* ctx, uint32_t* out_n);
+/* Increments [first, first + n) (a range beyond the table -> LB_ERR_INVALID_ARGUMENT). */
+int lb_balance_table_read(lb_ctx* ctx, uint32_t first, uint32_t n, uint8_t* out);
+/* The walk above for n_seeds seeds (seeds32: n_seeds x 32 bytes) over one active_indices[0..n)
+ * and the context's balance table.  out_indices: n_seeds x count; out_found, out_tried
+ * (optional): n_seeds.  Synchronous; waits for calls in flight; takes no slot and no ticket.
+ * n_seeds == 0 -> LB_OK, nothing done.
+ * store_list: LB_NO_LIST, or a list id (n_seeds must be 1): when the seed filled, list
+ * store_list becomes the count indices, copied on the device; when it did not, the list stays
+ * as it was.
+ * LB_ERR_INVALID_ARGUMENT (lb_last_error says which), no output written and no list changed:
+ * n == 0 (the reference throws), count == 0, n_seeds > LB_SAMPLE_MAX_SEEDS,
+ * count > LB_SAMPLE_MAX_COUNT, n > LB_SHUFFLE_MAX, max_increment outside [1, 255],
+ * max_candidates outside [1, LB_SAMPLE_MAX_CANDIDATES], a list id with n_seeds != 1 or
+ * >= LB_INDEX_LISTS, any active index >= the balance table's size (checked on the device over
+ * all n indices, whichever candidates get examined).
+ * lb_last_stage_times then reports one stage, sample. */
+int lb_sample_by_balance(lb_ctx* ctx, uint32_t n_seeds, const uint8_t* seeds32, uint32_t count, uint32_t n,
+                         const uint32_t* active_indices, uint32_t max_increment, uint32_t max_candidates,
+                         uint32_t store_list, uint32_t* out_indices, uint32_t* out_found, uint32_t* out_tried);
+/* lb_aggregate_pubkeys_indexed over list[first .. first + n), read where it lies
+ * (SyncCommittee.aggregatePubkey of a committee sampled on the device).  n == 0, an unknown
+ * list or a range beyond the list -> LB_ERR_INVALID_ARGUMENT; a list entry >= the pubkey
+ * table's size -> *out_status = LB_SET_BAD_ENCODING. */
+int lb_aggregate_pubkeys_list(lb_ctx* ctx, uint32_t list, uint32_t first, uint32_t n, uint8_t* out96,
+                              uint8_t* out_status);
+
 /* A set's keys by descriptor, one entry per set of a lb_request_batch whose pubkeys,
  * pk_offsets and pubkey_indices are all NULL.  Set i's keys are the validator indices the
  * entry lists, in list order, into the device pubkey table; the call is then exactly the

@@ -288,7 +288,11 @@ struct lb_ctx {
     uint32_t* d = nullptr;
     uint32_t n = 0, cap = 0;
   } lists[LB_INDEX_LISTS];
-  hipEvent_t list_ev[2] = {};  // lb_index_list_shuffle's stage time
+  hipEvent_t list_ev[2] = {};  // lb_index_list_shuffle's and lb_sample_by_balance's stage time
+  // device-resident balance table (EffectiveBalanceIncrements mirror, lb_balance_table_*): one
+  // byte per validator, what lb_sample_by_balance weighs its candidates by (k_sample.hip)
+  uint8_t* d_bal = nullptr;
+  uint32_t bal_n = 0, bal_cap = 0;
   // timing of the last completed verify call
   int n_stages = 0;
   float stage_ms[Slot::kMaxStages] = {};
@@ -1543,6 +1547,7 @@ int lb_destroy(lb_ctx* ctx) {
     if (l.d) (void)hipFree(l.d);
   for (hipEvent_t e : ctx->list_ev)
     if (e) (void)hipEventDestroy(e);
+  if (ctx->d_bal) (void)hipFree(ctx->d_bal);
   if (ctx->aux_stream) {
     (void)hipStreamSynchronize(ctx->aux_stream);
     (void)hipStreamDestroy(ctx->aux_stream);
@@ -2382,8 +2387,9 @@ int lb_decode_signatures(lb_ctx* ctx, uint32_t n, const uint8_t* sigs, const uin
 }
 
 // One aggregated key from `src` (n keys by bytes or by table index): Jacobian sum, serialized
+// (dev_indices: the indices where they already lie in HBM, a stretch of an index list)
 static int aggregate_pubkeys(lb_ctx* ctx, uint32_t n, const uint8_t* pks, const uint32_t* indices, uint8_t* out96,
-                             uint8_t* out_status) {
+                             uint8_t* out_status, const uint32_t* dev_indices = nullptr) {
   HelperCall c(ctx);
   const uint32_t off[2] = {0, n};
   uint8_t st = 0;
@@ -2394,7 +2400,9 @@ static int aggregate_pubkeys(lb_ctx* ctx, uint32_t n, const uint8_t* pks, const 
   auto d_out = c.out(out96, 96);
   auto d_st = c.out(&st, 1);
   LB_TRY(c.begin());
-  const PkSource src{d_p, d_idx, indices ? ctx->d_table : nullptr, indices ? ctx->table_n : 0};
+  const bool by_index = indices || dev_indices;
+  const PkSource src{d_p, dev_indices ? dev_indices : (const uint32_t*)d_idx, by_index ? ctx->d_table : nullptr,
+                     by_index ? ctx->table_n : 0};
   LB_LAUNCH(k_pubkeys_single, 1, TPB, 1u, src, d_off, d_pk, d_st);
   LB_LAUNCH(k_pubkeys_agg, 1, TPB, 1u, src, d_off, d_pk, d_st);
   LB_LAUNCH(k_g1_serialize, 1, TPB, 1u, (const g1j*)d_pk, d_out);
@@ -2604,6 +2612,180 @@ int lb_index_list_read(lb_ctx* ctx, uint32_t list, uint32_t first, uint32_t n, u
   LB_HIP(hipMemcpyAsync(out, ctx->lists[list].d + first, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost,
                         ctx->stream));
   LB_HIP(hipStreamSynchronize(ctx->stream));
+  return LB_OK;
+}
+
+int lb_aggregate_pubkeys_list(lb_ctx* ctx, uint32_t list, uint32_t first, uint32_t n, uint8_t* out96,
+                              uint8_t* out_status) {
+  if (!ctx || !out96 || list >= LB_INDEX_LISTS) return LB_ERR_INVALID_ARGUMENT;
+  if (n == 0) {
+    ctx->err = "EMPTY_AGGREGATE_ARRAY";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  if ((uint64_t)first + n > ctx->lists[list].n) {
+    ctx->err = "lb_aggregate_pubkeys_list: first + n beyond the index list";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  return aggregate_pubkeys(ctx, n, nullptr, nullptr, out96, out_status, ctx->lists[list].d + first);
+}
+
+// ---- device-resident balance table (EffectiveBalanceIncrements mirror) -----------------
+int lb_balance_table_put(lb_ctx* ctx, uint32_t first, uint32_t n, const uint8_t* increments) {
+  if (!ctx || (n && !increments)) return LB_ERR_INVALID_ARGUMENT;
+  if (first > ctx->bal_n || (uint64_t)first + n > 0x7fffffffu) {
+    ctx->err = "lb_balance_table_put: first beyond the table's size";
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  if (n == 0) return LB_OK;
+  LB_HIP(hipSetDevice(ctx->device));
+  LB_TRY(helper_slot(ctx));  // (nothing in flight reads the table; the order of calls is kept all the same)
+  const uint32_t need = first + n;
+  if (need > ctx->bal_cap) {
+    uint64_t cap = (uint64_t)ctx->bal_cap * 2;
+    if (cap < need) cap = need;
+    if (cap < 4096) cap = 4096;
+    uint8_t* d = nullptr;
+    if (hipMalloc(&d, cap) != hipSuccess) {
+      ctx->err = "hipMalloc balance table failed";
+      return LB_ERR_OUT_OF_MEMORY;
+    }
+    if (ctx->bal_n) LB_HIP(hipMemcpyAsync(d, ctx->d_bal, ctx->bal_n, hipMemcpyDeviceToDevice, ctx->stream));
+    LB_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->d_bal) LB_HIP(hipFree(ctx->d_bal));
+    ctx->d_bal = d;
+    ctx->bal_cap = (uint32_t)cap;
+  }
+  LB_HIP(hipMemcpyAsync(ctx->d_bal + first, increments, n, hipMemcpyHostToDevice, ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  if (need > ctx->bal_n) ctx->bal_n = need;
+  return LB_OK;
+}
+
+int lb_balance_table_size(const lb_ctx* ctx, uint32_t* out_n) {
+  if (!ctx || !out_n) return LB_ERR_INVALID_ARGUMENT;
+  *out_n = ctx->bal_n;
+  return LB_OK;
+}
+
+int lb_balance_table_read(lb_ctx* ctx, uint32_t first, uint32_t n, uint8_t* out) {
+  if (!ctx || (n && !out) || (uint64_t)first + n > ctx->bal_n) return LB_ERR_INVALID_ARGUMENT;
+  if (n == 0) return LB_OK;
+  LB_HIP(hipSetDevice(ctx->device));
+  LB_HIP(hipMemcpyAsync(out, ctx->d_bal + first, n, hipMemcpyDeviceToHost, ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  return LB_OK;
+}
+
+// ---- balance-weighted sampling: proposers, the sync committee (k_sample.hip) -------------
+// The size of the pass behind one of `pass` candidates per seed: twice it, within
+// LB_SAMPLE_PASS_MAX and 2^20 candidates over all seeds (the scratch of a pass: 5 bytes each)
+static uint32_t sample_next_pass(uint32_t pass, uint32_t n_seeds) {
+  uint32_t cap = (1u << 20) / n_seeds;  // (n_seeds <= 64: at least 16,384, a multiple of 64)
+  if (cap > LB_SAMPLE_PASS_MAX) cap = LB_SAMPLE_PASS_MAX;
+  return pass * 2 < cap ? pass * 2 : cap;
+}
+
+int lb_sample_by_balance(lb_ctx* ctx, uint32_t n_seeds, const uint8_t* seeds32, uint32_t count, uint32_t n,
+                         const uint32_t* active, uint32_t max_inc, uint32_t max_candidates, uint32_t store_list,
+                         uint32_t* out_indices, uint32_t* out_found, uint32_t* out_tried) {
+  if (!ctx) return LB_ERR_INVALID_ARGUMENT;
+  if (n_seeds == 0) return LB_OK;
+  const char* why = nullptr;
+  if (!seeds32 || !active || !out_indices)
+    why = "a null buffer";
+  else if (n == 0)
+    why = "no active indices";
+  else if (count == 0)
+    why = "count == 0";
+  else if (n_seeds > LB_SAMPLE_MAX_SEEDS)
+    why = "more than LB_SAMPLE_MAX_SEEDS seeds";
+  else if (count > LB_SAMPLE_MAX_COUNT)
+    why = "count above LB_SAMPLE_MAX_COUNT";
+  else if (n > LB_SHUFFLE_MAX)
+    why = "more than LB_SHUFFLE_MAX indices";
+  else if (max_inc < 1 || max_inc > 255)
+    why = "max_increment outside [1, 255]";
+  else if (max_candidates < 1 || max_candidates > LB_SAMPLE_MAX_CANDIDATES)
+    why = "max_candidates outside [1, LB_SAMPLE_MAX_CANDIDATES]";
+  else if (store_list != LB_NO_LIST && store_list >= LB_INDEX_LISTS)
+    why = "unknown index list";
+  else if (store_list != LB_NO_LIST && n_seeds != 1)
+    why = "a list is stored from one seed";
+  if (why) {
+    ctx->err = std::string("lb_sample_by_balance: ") + why;
+    return LB_ERR_INVALID_ARGUMENT;
+  }
+  ctx->n_stages = 0;
+  LB_HIP(hipSetDevice(ctx->device));
+  for (hipEvent_t& e : ctx->list_ev)
+    if (!e) LB_HIP(hipEventCreate(&e));
+  // the largest pass this call can come to, which is its last: the scratch is carved once
+  // (the first pass is at most 4,096 and the bound at least 16,384, so no pass is smaller than the one before)
+  uint32_t pass = LB_SAMPLE_FIRST_PASS(count), pass_max = pass;
+  for (uint32_t seen = pass; seen < max_candidates; seen += pass_max) pass_max = sample_next_pass(pass_max, n_seeds);
+  HelperCall c(ctx);
+  auto d_active = c.in(active, n);
+  auto d_seeds = c.in(seeds32, (size_t)n_seeds * 32);
+  auto d_pivots = c.scratch<uint32_t>((size_t)n_seeds * LB_SHUFFLE_ROUNDS);
+  auto d_state = c.scratch<uint32_t>(1 + 2 * (size_t)n_seeds);  // max index; found[]; tried[]
+  auto d_out = c.scratch<uint32_t>((size_t)n_seeds * count);
+  auto d_cand = c.scratch<uint32_t>((size_t)n_seeds * pass_max);
+  auto d_acc = c.scratch<uint8_t>((size_t)n_seeds * pass_max);
+  LB_TRY(c.begin());
+  uint32_t* const d_max = d_state;
+  uint32_t* const d_found = d_max + 1;
+  uint32_t* const d_tried = d_found + n_seeds;
+  const bool timed = ctx->ccfg.stage_events;
+  if (timed) LB_HIP(hipEventRecord(ctx->list_ev[0], ctx->stream));
+  LB_HIP(hipMemsetAsync(d_state, 0, sizeof(uint32_t) * (1 + 2 * (size_t)n_seeds), ctx->stream));
+  LB_HIP(hipMemsetAsync(d_out, 0xff, sizeof(uint32_t) * (size_t)n_seeds * count, ctx->stream));  // LB_SAMPLE_NONE
+  const uint32_t range_blocks = blocks_for(n, LB_LISTS_TPB);
+  LB_LAUNCH(k_sample_range, range_blocks < 1024u ? range_blocks : 1024u, LB_LISTS_TPB, n, d_active, d_max);
+  LB_LAUNCH(k_sample_pivots, blocks_for(n_seeds * LB_SHUFFLE_ROUNDS, LB_LISTS_TPB), LB_LISTS_TPB, n_seeds, n, d_seeds,
+            d_pivots);
+  uint32_t state[1 + 2 * LB_SAMPLE_MAX_SEEDS];
+  uint32_t* const found = state + 1;
+  for (uint32_t base = 0; base < max_candidates; base += pass, pass = sample_next_pass(pass, n_seeds)) {
+    LB_ENQUEUE(ctx->stream, k_sample_candidates, dim3(blocks_for(pass, LB_LISTS_TPB), n_seeds), LB_LISTS_TPB, n, count,
+               base, pass, max_candidates, max_inc, d_seeds, (const uint32_t*)d_pivots, d_active,
+               (const uint8_t*)ctx->d_bal, ctx->bal_n, (const uint32_t*)d_found, d_cand, d_acc);
+    LB_LAUNCH(k_sample_select, n_seeds, LB_LISTS_TPB, count, base, pass, (const uint32_t*)d_cand,
+              (const uint8_t*)d_acc, d_out, d_found, d_tried);
+    LB_HIP(hipMemcpyAsync(state, d_state, sizeof(uint32_t) * (1 + (size_t)n_seeds), hipMemcpyDeviceToHost,
+                          ctx->stream));
+    LB_HIP(hipStreamSynchronize(ctx->stream));
+    if (state[0] >= ctx->bal_n) {  // (the candidates kernel read no increment outside the table)
+      ctx->err = "lb_sample_by_balance: an active index at or beyond the balance table's size";
+      return LB_ERR_INVALID_ARGUMENT;
+    }
+    bool filled = true;
+    for (uint32_t s = 0; s < n_seeds; s++) filled = filled && found[s] >= count;
+    if (filled) break;
+  }
+  if (timed) LB_HIP(hipEventRecord(ctx->list_ev[1], ctx->stream));
+  if (store_list != LB_NO_LIST && found[0] == count) {  // device to device; an unfilled seed leaves the list
+    lb_ctx::IndexList& L = ctx->lists[store_list];
+    LB_TRY(list_reserve(ctx, L, count));
+    L.n = 0;  // (until the copy is known to have run)
+    LB_HIP(hipMemcpyAsync(L.d, d_out, sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToDevice, ctx->stream));
+    LB_HIP(hipStreamSynchronize(ctx->stream));
+    L.n = count;
+  }
+  LB_HIP(hipMemcpyAsync(out_indices, d_out, sizeof(uint32_t) * (size_t)n_seeds * count, hipMemcpyDeviceToHost,
+                        ctx->stream));
+  LB_HIP(hipMemcpyAsync(state + 1 + n_seeds, d_tried, sizeof(uint32_t) * (size_t)n_seeds, hipMemcpyDeviceToHost,
+                        ctx->stream));
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  for (uint32_t s = 0; s < n_seeds; s++) {
+    if (out_found) out_found[s] = found[s];
+    if (out_tried) out_tried[s] = found[s] == count ? state[1 + n_seeds + s] : max_candidates;
+  }
+  if (timed) {
+    LB_HIP(hipEventElapsedTime(&ctx->stage_ms[0], ctx->list_ev[0], ctx->list_ev[1]));
+    ctx->stage_name[0] = "sample";
+    ctx->stage_ops[0] = 0;
+    ctx->n_stages = 1;
+  }
   return LB_OK;
 }
 

@@ -362,4 +362,20 @@ __global__ void __launch_bounds__(LB_LISTS_TPB) k_expand_keys(uint32_t n_sets, c
                                                               const uint8_t* __restrict__ bits, IndexLists lists,
                                                               const uint32_t* __restrict__ pk_off,
                                                               uint32_t* __restrict__ idx);
+// balance-weighted sampling over the shuffle (k_sample.hip): proposers, the sync committee
+__global__ void __launch_bounds__(LB_LISTS_TPB) k_sample_range(uint32_t n, const uint32_t* __restrict__ active,
+                                                               uint32_t* __restrict__ max_index);
+__global__ void __launch_bounds__(LB_LISTS_TPB) k_sample_pivots(uint32_t n_seeds, uint32_t n,
+                                                                const uint8_t* __restrict__ seeds,
+                                                                uint32_t* __restrict__ pivots);
+__global__ void __launch_bounds__(LB_LISTS_TPB)
+    k_sample_candidates(uint32_t n, uint32_t count, uint32_t base, uint32_t pass, uint32_t max_candidates,
+                        uint32_t max_inc, const uint8_t* __restrict__ seeds, const uint32_t* __restrict__ pivots,
+                        const uint32_t* __restrict__ active, const uint8_t* __restrict__ inc, uint32_t inc_n,
+                        const uint32_t* __restrict__ found, uint32_t* __restrict__ cand,
+                        uint8_t* __restrict__ accept);
+__global__ void __launch_bounds__(LB_LISTS_TPB)
+    k_sample_select(uint32_t count, uint32_t base, uint32_t pass, const uint32_t* __restrict__ cand,
+                    const uint8_t* __restrict__ accept, uint32_t* __restrict__ out, uint32_t* __restrict__ found,
+                    uint32_t* __restrict__ tried);
 }  // namespace lb

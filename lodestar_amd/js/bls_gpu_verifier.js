@@ -705,6 +705,29 @@ class BlsGpuVerifier {
     this.keyMap.lbLists.set(listId, ix);
   }
 
+  /** EffectiveBalanceIncrements (cache/effectiveBalanceIncrements.ts:8) to every GPU's balance
+   * table: overwrite or append from validator index `first`; resolves to the table's size. */
+  async syncBalances(increments, first = 0) {
+    return backendSyncBalances(this.backends, increments, first);
+  }
+
+  /** computeProposers (state-transition/src/util/seed.ts:22-80) on the GPU: the proposer of each
+   * of `slots` slots from startSlot, sampled by balance from the device's table; -1 where a slot
+   * found none among its activeIndices.length candidates. */
+  async computeProposers(epochSeed, startSlot, activeIndices, slots = 32, maxIncrement = 32) {
+    return backendComputeProposers(this.backends[0], epochSeed, startSlot, activeIndices, slots, maxIncrement);
+  }
+
+  /** getNextSyncCommitteeIndices (seed.ts:92-126) and getNextSyncCommittee's aggregatePubkey
+   * (util/syncCommittee.ts:21-38) on the GPU: index list `listId` of every GPU becomes the
+   * committee's `size` validator indices; resolves to {indices, aggregatePubkey (96 bytes)}.
+   * Rejects when the committee did not fill within maxCandidates (the reference would loop). */
+  async syncCommittee(listId, activeIndices, seed, size = 512, maxIncrement = 32,
+    maxCandidates = SAMPLE_MAX_CANDIDATES) {
+    return backendSyncCommittee(this.backends, this.keyMap, listId, activeIndices, seed, size, maxIncrement,
+      maxCandidates);
+  }
+
   /** pubkeyCache.syncPubkeys (pubkeyCache.ts:56-77) for the GPUs: mirror the entries of
    * index2pubkey (PublicKey objects) not mirrored yet -- index2pubkey[i] maps to table
    * entry base + i, where base is the table size at the first call -- and return the
@@ -1064,6 +1087,49 @@ class BlsGpuVerifier {
   }
 }
 
+// ---- balance-weighted sampling (lb_sample_by_balance): proposers, the sync committee ----------
+const SAMPLE_NONE = 0xffffffff;
+const SAMPLE_MAX_CANDIDATES = 4194304;
+
+/** computeProposers' per-slot seeds (state-transition/src/util/seed.ts:34): SHA256(epochSeed || LE64(slot)) */
+function proposerSlotSeeds(epochSeed, startSlot, slots) {
+  const seeds = new Uint8Array(32 * slots);
+  for (let i = 0; i < slots; i++) {
+    const le = Buffer.alloc(8);
+    le.writeBigUInt64LE(BigInt(startSlot + i));
+    seeds.set(crypto.createHash("sha256").update(epochSeed).update(le).digest(), 32 * i);
+  }
+  return seeds;
+}
+
+async function backendSyncBalances(backends, increments, first) {
+  const inc = increments instanceof Uint8Array ? increments : Uint8Array.from(increments);
+  const sizes = await Promise.all(backends.map((b) => b.balanceTablePut(first, inc)));
+  if (sizes.some((n) => n !== sizes[0])) throw new Error("balance tables out of sync across devices: " + sizes);
+  return sizes[0];
+}
+
+async function backendComputeProposers(backend, epochSeed, startSlot, activeIndices, slots, maxIncrement) {
+  const active = activeIndices instanceof Uint32Array ? activeIndices : Uint32Array.from(activeIndices);
+  const r = await backend.sampleByBalance({seeds: proposerSlotSeeds(epochSeed, startSlot, slots), count: 1,
+    activeIndices: active, maxIncrement, maxCandidates: active.length});
+  return Array.from(r.indices, (v) => (v === SAMPLE_NONE ? -1 : v));
+}
+
+async function backendSyncCommittee(backends, keyMap, listId, activeIndices, seed, size, maxIncrement, maxCandidates) {
+  const active = activeIndices instanceof Uint32Array ? activeIndices : Uint32Array.from(activeIndices);
+  const outs = await Promise.all(backends.map((b) => b.sampleByBalance({seeds: seed, count: size, activeIndices: active,
+    maxIncrement, maxCandidates, storeList: listId, aggregate: true})));
+  const r = outs[0];
+  if (r.found[0] !== size) {
+    throw new Error("sync committee not filled: " + r.found[0] + " of " + size + " accepted among " + maxCandidates +
+      " candidates");
+  }
+  keyMap.lbLists = keyMap.lbLists || new Map();
+  keyMap.lbLists.set(listId, r.indices);
+  return {indices: r.indices, aggregatePubkey: r.aggregatePubkey};
+}
+
 /** BlsSingleThreadVerifier (chain/bls/singleThread.ts:10-89) on one GPU: no queue,
  * no buffering, every call goes straight to the device. */
 class BlsGpuSingleThreadVerifier {
@@ -1090,6 +1156,18 @@ class BlsGpuSingleThreadVerifier {
     await this.backend.indexListPut(listId, ix);
     this.keyMap.lbLists = this.keyMap.lbLists || new Map();
     this.keyMap.lbLists.set(listId, ix);
+  }
+  /** as BlsGpuVerifier.syncBalances / computeProposers / syncCommittee, on this verifier's one GPU */
+  async syncBalances(increments, first = 0) {
+    return backendSyncBalances([this.backend], increments, first);
+  }
+  async computeProposers(epochSeed, startSlot, activeIndices, slots = 32, maxIncrement = 32) {
+    return backendComputeProposers(this.backend, epochSeed, startSlot, activeIndices, slots, maxIncrement);
+  }
+  async syncCommittee(listId, activeIndices, seed, size = 512, maxIncrement = 32,
+    maxCandidates = SAMPLE_MAX_CANDIDATES) {
+    return backendSyncCommittee([this.backend], this.keyMap, listId, activeIndices, seed, size, maxIncrement,
+      maxCandidates);
   }
   /** as BlsGpuVerifier.syncPubkeys / syncIndex2pubkey, on this verifier's one GPU */
   async syncPubkeys(keys, pkLen = 48) {

@@ -136,6 +136,20 @@ export interface GpuBackend {
   indexListPut?(listId: number, indices: Uint32Array): Promise<number>;
   /** lb_index_list_shuffle: resolves to unshuffleList(activeIndices, seed), which list `listId` now holds */
   indexListShuffle?(listId: number, activeIndices: Uint32Array, seed: Uint8Array): Promise<Uint32Array>;
+  /** lb_balance_table_put: resolves to the balance table's size */
+  balanceTablePut?(first: number, increments: Uint8Array): Promise<number>;
+  /** lb_sample_by_balance (seeds: 32 bytes each); indices: seeds x count, 0xFFFFFFFF where unfilled.
+   * storeList: a lone seed's filled result replaces that index list on the device; with aggregate,
+   * aggregatePubkey is lb_aggregate_pubkeys_list of the stored list (96 bytes) */
+  sampleByBalance?(req: {
+    seeds: Uint8Array;
+    count: number;
+    activeIndices: Uint32Array;
+    maxIncrement: number;
+    maxCandidates: number;
+    storeList?: number;
+    aggregate?: boolean;
+  }): Promise<{indices: Uint32Array; found: Uint32Array; tried: Uint32Array; aggregatePubkey?: Uint8Array}>;
   aggregatePubkeys?(keys: Uint8Array | Uint32Array): Promise<Uint8Array>;
   /** KZG_SETUP_G2_MONOMIAL[1], 96 bytes compressed; a refused point rejects and keeps the old setup */
   kzgLoadSetup?(g2Tau: Uint8Array): Promise<void>;
@@ -219,6 +233,25 @@ export class BlsGpuVerifier implements IBlsVerifier {
   syncShuffling(listId: number, activeIndices: Uint32Array | number[], seed: Uint8Array): Promise<Uint32Array>;
   /** indices as given (a sync committee's 512) as index list `listId` */
   putIndexList(listId: number, indices: Uint32Array | number[]): Promise<void>;
+  /** EffectiveBalanceIncrements to every GPU's balance table, from validator index `first`; the table's size */
+  syncBalances(increments: Uint8Array | number[], first?: number): Promise<number>;
+  /** computeProposers (util/seed.ts:22-80) on the GPU; -1 where a slot found no proposer */
+  computeProposers(
+    epochSeed: Uint8Array,
+    startSlot: number,
+    activeIndices: Uint32Array | number[],
+    slots?: number,
+    maxIncrement?: number
+  ): Promise<number[]>;
+  /** getNextSyncCommitteeIndices + aggregatePubkey on the GPU; the committee becomes index list `listId` */
+  syncCommittee(
+    listId: number,
+    activeIndices: Uint32Array | number[],
+    seed: Uint8Array,
+    size?: number,
+    maxIncrement?: number,
+    maxCandidates?: number
+  ): Promise<{indices: Uint32Array; aggregatePubkey: Uint8Array}>;
   /** pubkeyCache.syncPubkeys for the GPUs: mirror index2pubkey's new entries (incremental);
    * returns the number of entries mirrored. */
   syncIndex2pubkey(index2pubkey: PublicKeyLike[]): Promise<number>;
@@ -259,6 +292,25 @@ export class BlsGpuSingleThreadVerifier implements IBlsVerifier {
   syncShuffling(listId: number, activeIndices: Uint32Array | number[], seed: Uint8Array): Promise<Uint32Array>;
   /** indices as given (a sync committee's 512) as index list `listId` */
   putIndexList(listId: number, indices: Uint32Array | number[]): Promise<void>;
+  /** EffectiveBalanceIncrements to every GPU's balance table, from validator index `first`; the table's size */
+  syncBalances(increments: Uint8Array | number[], first?: number): Promise<number>;
+  /** computeProposers (util/seed.ts:22-80) on the GPU; -1 where a slot found no proposer */
+  computeProposers(
+    epochSeed: Uint8Array,
+    startSlot: number,
+    activeIndices: Uint32Array | number[],
+    slots?: number,
+    maxIncrement?: number
+  ): Promise<number[]>;
+  /** getNextSyncCommitteeIndices + aggregatePubkey on the GPU; the committee becomes index list `listId` */
+  syncCommittee(
+    listId: number,
+    activeIndices: Uint32Array | number[],
+    seed: Uint8Array,
+    size?: number,
+    maxIncrement?: number,
+    maxCandidates?: number
+  ): Promise<{indices: Uint32Array; aggregatePubkey: Uint8Array}>;
   syncIndex2pubkey(index2pubkey: PublicKeyLike[]): Promise<number>;
   verifySignatureSets(sets: ISignatureSet[]): Promise<boolean>;
   verifySignatureSetsSameMessage(

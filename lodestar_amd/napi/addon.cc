@@ -174,7 +174,8 @@ void check_offsets(const std::vector<uint32_t>& off, size_t n, uint32_t last, co
 
 // ---- tasks ---------------------------------------------------------------------
 enum class Kind {
-  Verify, Partial, Finish, SameMessage, SyncPubkeys, AggPubkeys, AggSigGroups, GtCheck, KzgLoad, KzgVerify, KzgLoadG1, KzgCommit, KzgProve, KzgPoint, IndexListPut, IndexListShuffle, Close
+  Verify, Partial, Finish, SameMessage, SyncPubkeys, AggPubkeys, AggSigGroups, GtCheck, KzgLoad, KzgVerify, KzgLoadG1, KzgCommit, KzgProve, KzgPoint, IndexListPut, IndexListShuffle,
+  BalancePut, Sample, Close
 };
 
 struct Task {
@@ -197,6 +198,13 @@ struct Task {
   // indexListPut / indexListShuffle: the list id, the indices in (pk_idx) and the shuffling out
   uint32_t list_id = 0;
   std::vector<uint32_t> list_out;
+  // balanceTablePut: increments in pubkeys, first in u32 (the table's size comes back in it).
+  // sampleByBalance: seeds in seed (n_jobs of them), the active indices in pk_idx, list_id the list
+  // to store (LB_NO_LIST: none); indices out in list_out, found / tried per seed, and with
+  // want_agg the stored list's aggregate key in out_bytes (filled: has_agg)
+  uint32_t s_count = 0, s_max_inc = 0, s_max_cand = 0;
+  bool want_agg = false, has_agg = false;
+  std::vector<uint32_t> s_found, s_tried;
   // verifySameMessage(batch, {aggregate, mask}): the jobs' aggregate signatures as well;
   // aggregateSignatureGroups: groups in job_off, noCheck in no_check
   bool agg = false, has_mask = false, no_check = false;
@@ -428,6 +436,21 @@ void lane_loop(Context* c) {
         c->lane_ok = false;
         fprintf(stderr, "lodestar_bls: latency lane retired (its index lists could not follow: %s); priority "
                         "calls run on the main context\n", lb_last_error(c->lctx));
+      }
+      complete(c, t);
+      continue;
+    }
+    if (t->kind == Kind::BalancePut || t->kind == Kind::Sample) {
+      // (the lane's balance table mirrors ctx's; a sampled committee arrives computed, as a shuffling does)
+      const int rc = !c->lane_ok ? LB_OK
+                     : t->kind == Kind::BalancePut
+                         ? lb_balance_table_put(c->lctx, (uint32_t)t->i32, t->n_keys, t->pubkeys.data())
+                         : lb_index_list_put(c->lctx, t->list_id, t->s_count, t->list_out.data());
+      if (rc != LB_OK) {
+        c->lane_ok = false;
+        fprintf(stderr, "lodestar_bls: latency lane retired (its %s could not follow: %s); priority calls run on "
+                        "the main context\n", t->kind == Kind::BalancePut ? "balance table" : "index lists",
+                lb_last_error(c->lctx));
       }
       complete(c, t);
       continue;
@@ -695,6 +718,47 @@ void worker_loop(Context* c) {
         complete(c, t);
         break;
       }
+      case Kind::BalancePut:
+      case Kind::Sample: {
+        int rc;
+        bool mirror = true;  // the lane's context follows (a committee only when it was stored)
+        if (t->kind == Kind::BalancePut) {
+          t->i32 = (int32_t)t->u32;  // (first, for the lane: u32 becomes the size)
+          rc = lb_balance_table_put(c->ctx, t->u32, t->n_keys, t->pubkeys.data());
+          if (rc == LB_OK) rc = lb_balance_table_size(c->ctx, &t->u32);
+        } else {
+          const size_t n_out = (size_t)t->n_jobs * t->s_count;
+          t->list_out.assign(n_out ? n_out : 1, LB_SAMPLE_NONE);
+          t->s_found.assign(t->n_jobs ? t->n_jobs : 1, 0);
+          t->s_tried.assign(t->n_jobs ? t->n_jobs : 1, 0);
+          rc = lb_sample_by_balance(c->ctx, t->n_jobs, t->seed.data(), t->s_count, t->n_keys, t->pk_idx.data(),
+                                    t->s_max_inc, t->s_max_cand, t->list_id, t->list_out.data(), t->s_found.data(),
+                                    t->s_tried.data());
+          mirror = rc == LB_OK && t->list_id != LB_NO_LIST && t->n_jobs == 1 && t->s_found[0] == t->s_count;
+          if (mirror && t->want_agg) {
+            t->out_bytes.assign(LB_PUBKEY_BYTES, 0);
+            uint8_t st = 0;
+            rc = lb_aggregate_pubkeys_list(c->ctx, t->list_id, 0, t->s_count, t->out_bytes.data(), &st);
+            t->has_agg = rc == LB_OK && st == LB_SET_OK;
+            if (rc == LB_OK && st != LB_SET_OK) {
+              t->rc = LB_ERR_INVALID_ARGUMENT;
+              t->errmsg = "invalid pubkey";
+            }
+          }
+        }
+        if (rc != LB_OK) {
+          fail(t, rc, c->ctx);
+        } else if (mirror && c->lctx && c->lane_ok) {
+          {
+            std::lock_guard<std::mutex> lk(c->lmu);
+            c->lqueue.push_back(t);
+          }
+          c->lcv.notify_one();
+          break;
+        }
+        complete(c, t);
+        break;
+      }
       case Kind::AggPubkeys: {
         t->out_bytes.assign(LB_PUBKEY_BYTES, 0);
         uint8_t st = 0;
@@ -946,6 +1010,18 @@ void call_js(napi_env env, napi_value /*cb*/, void* context, void* data) {
         break;
       case Kind::IndexListShuffle:
         result = make_words(env, napi_uint32_array, t->list_out.data(), t->n_keys);
+        break;
+      case Kind::BalancePut:
+        napi_create_uint32(env, t->u32, &result);
+        break;
+      case Kind::Sample:
+        napi_create_object(env, &result);
+        napi_set_named_property(env, result, "indices",
+                                make_words(env, napi_uint32_array, t->list_out.data(), (size_t)t->n_jobs * t->s_count));
+        napi_set_named_property(env, result, "found", make_words(env, napi_uint32_array, t->s_found.data(), t->n_jobs));
+        napi_set_named_property(env, result, "tried", make_words(env, napi_uint32_array, t->s_tried.data(), t->n_jobs));
+        if (t->has_agg)
+          napi_set_named_property(env, result, "aggregatePubkey", make_u8(env, t->out_bytes.data(), LB_PUBKEY_BYTES));
         break;
       case Kind::GtCheck:
         napi_get_boolean(env, t->i32 != 0, &result);
@@ -1250,6 +1326,73 @@ napi_value IndexListShuffle(napi_env env, napi_callback_info info) {
   return m_index_list(env, info, Kind::IndexListShuffle);
 }
 
+// balanceTablePut(first, increments: Uint8Array) -> Promise<number> (the table's size)
+napi_value BalanceTablePut(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  Context* c = unwrap(env, info, &argc, argv);
+  Task* t = new Task();
+  t->kind = Kind::BalancePut;
+  try {
+    if (!c || argc < 2) throw ArgError{"balanceTablePut(first, increments: Uint8Array)"};
+    if (napi_get_value_uint32(env, argv[0], &t->u32) != napi_ok) throw ArgError{"first must be a number"};
+    typed(env, argv[1], napi_uint8_array, "increments", t->pubkeys);
+    t->n_keys = (uint32_t)t->pubkeys.size();
+    if (t->pubkeys.empty()) t->pubkeys.push_back(0);
+  } catch (const ArgError& e) {
+    delete t;
+    return rejected(env, e.msg);
+  }
+  return submit(env, c, t);
+}
+
+// sampleByBalance({seeds: Uint8Array(32 k), count, activeIndices: Uint32Array, maxIncrement, maxCandidates,
+//                  storeList?, aggregate?}) -> Promise<{indices, found, tried, aggregatePubkey?}>
+napi_value SampleByBalance(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  Context* c = unwrap(env, info, &argc, argv);
+  Task* t = new Task();
+  t->kind = Kind::Sample;
+  try {
+    napi_valuetype ty = napi_undefined;
+    if (c && argc >= 1) napi_typeof(env, argv[0], &ty);
+    if (ty != napi_object)
+      throw ArgError{"sampleByBalance({seeds, count, activeIndices, maxIncrement, maxCandidates, storeList?, "
+                     "aggregate?})"};
+    napi_value o = argv[0], v;
+    req_typed(env, o, "seeds", napi_uint8_array, t->seed);
+    if (t->seed.size() % 32) throw ArgError{"seeds: 32 bytes each"};
+    t->n_jobs = (uint32_t)(t->seed.size() / 32);
+    if (t->seed.empty()) t->seed.push_back(0);
+    req_typed(env, o, "activeIndices", napi_uint32_array, t->pk_idx);
+    t->n_keys = (uint32_t)t->pk_idx.size();
+    if (t->pk_idx.empty()) t->pk_idx.push_back(0);
+    const auto num = [&](const char* name, uint32_t* out) {
+      if (!has_prop(env, o, name, &v) || napi_get_value_uint32(env, v, out) != napi_ok)
+        throw ArgError{std::string(name) + " must be a number"};
+    };
+    num("count", &t->s_count);
+    num("maxIncrement", &t->s_max_inc);
+    num("maxCandidates", &t->s_max_cand);
+    t->list_id = LB_NO_LIST;
+    if (has_prop(env, o, "storeList", &v)) {
+      napi_valuetype vt;
+      napi_typeof(env, v, &vt);
+      if (vt != napi_undefined && vt != napi_null && napi_get_value_uint32(env, v, &t->list_id) != napi_ok)
+        throw ArgError{"storeList must be a number"};
+    }
+    if (has_prop(env, o, "aggregate", &v)) napi_get_value_bool(env, v, &t->want_agg);
+    // (the output is sized here: the library's own limits refuse anything larger)
+    if (t->s_count > LB_SAMPLE_MAX_COUNT) throw ArgError{"count above LB_SAMPLE_MAX_COUNT"};
+    if (t->n_jobs > LB_SAMPLE_MAX_SEEDS) throw ArgError{"more than LB_SAMPLE_MAX_SEEDS seeds"};
+  } catch (const ArgError& e) {
+    delete t;
+    return rejected(env, e.msg);
+  }
+  return submit(env, c, t);
+}
+
 napi_value AggregatePubkeys(napi_env env, napi_callback_info info) {
   size_t argc = 1;
   napi_value argv[1];
@@ -1541,6 +1684,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"syncPubkeys", nullptr, SyncPubkeys, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"indexListPut", nullptr, IndexListPut, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"indexListShuffle", nullptr, IndexListShuffle, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"balanceTablePut", nullptr, BalanceTablePut, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"sampleByBalance", nullptr, SampleByBalance, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"aggregatePubkeys", nullptr, AggregatePubkeys, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"aggregateSignatureGroups", nullptr, AggregateSignatureGroups, nullptr, nullptr, nullptr, napi_default,
        nullptr},

@@ -51,6 +51,8 @@ EXPORTED_SYMBOLS = (
     "lb_index_list_put", "lb_index_list_shuffle", "lb_index_list_size", "lb_index_list_read",
     "lb_verify_requests_keys", "lb_verify_requests_keys_async", "lb_verify_requests_keys_priority_async",
     "lb_verify_requests_keys_partial_async", "lb_expand_set_keys",
+    "lb_balance_table_put", "lb_balance_table_size", "lb_balance_table_read", "lb_sample_by_balance",
+    "lb_aggregate_pubkeys_list",
 )
 
 # device-resident index lists and set keys by descriptor (lb_index_list_*, lb_verify_requests_keys*)
@@ -61,6 +63,29 @@ LB_KEYS_SLICE = 1
 LB_KEYS_BITS = 2
 # one lb_set_keys per set: kind, list, a, len, bits_off
 SET_KEYS_DTYPE = np.dtype([("kind", "<u4"), ("list", "<u4"), ("a", "<u4"), ("len", "<u4"), ("bits_off", "<u4")])
+
+# balance-weighted sampling (lb_sample_by_balance)
+LB_SAMPLE_MAX_SEEDS = 64
+LB_SAMPLE_MAX_COUNT = 2048
+LB_SAMPLE_MAX_CANDIDATES = 4194304
+LB_SAMPLE_NONE = 0xFFFFFFFF
+LB_NO_LIST = 0xFFFFFFFF
+LB_SAMPLE_PASS_MAX = 65536
+
+
+def sample_first_pass(count: int) -> int:
+    """LB_SAMPLE_FIRST_PASS: the candidates per seed of a call's first pass (each later pass is
+    twice the last, up to LB_SAMPLE_PASS_MAX)."""
+    return 64 if count == 1 else (2 * count + 63) // 64 * 64
+
+
+@dataclass
+class SampleResult:
+    """lb_sample_by_balance: indices[n_seeds][count] (LB_SAMPLE_NONE where unfilled), found and tried per seed."""
+    indices: np.ndarray
+    found: np.ndarray
+    tried: np.ndarray
+
 
 # blob KZG proof verification (lb_kzg_*)
 LB_KZG_BLOB_BYTES = 131072
@@ -261,6 +286,11 @@ def load_library() -> ctypes.CDLL:
         getattr(lib, name).argtypes = [vp, ctypes.POINTER(_RequestBatch), ctypes.POINTER(_KeySource), vp, vp, vp,
                                        ctypes.POINTER(ctypes.c_uint64)]
     lib.lb_expand_set_keys.argtypes = [vp, u32, ctypes.POINTER(_KeySource), vp, vp, u32]
+    lib.lb_balance_table_put.argtypes = [vp, u32, u32, vp]
+    lib.lb_balance_table_size.argtypes = [vp, ctypes.POINTER(u32)]
+    lib.lb_balance_table_read.argtypes = [vp, u32, u32, vp]
+    lib.lb_sample_by_balance.argtypes = [vp, u32, vp, u32, u32, vp, u32, u32, u32, vp, vp, vp]
+    lib.lb_aggregate_pubkeys_list.argtypes = [vp, u32, u32, u32, vp, vp]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name).restype = getattr(lib, name).restype or ctypes.c_int
     _lib = lib
@@ -556,6 +586,59 @@ class Device:
         out = np.zeros(max(n, 1), np.uint32)
         self._check(self.lib.lb_index_list_read(self._h, list_id, first, n, _ptr(out)), "lb_index_list_read")
         return out[:n]
+
+    def balance_table_put(self, increments, first: int = 0) -> int:
+        """lb_balance_table_put: overwrite or append effective-balance increments (one byte per
+        validator) from validator index `first` on; returns the table's size."""
+        a = _u8(increments)
+        buf = a if len(a) else np.zeros(1, np.uint8)
+        self._check(self.lib.lb_balance_table_put(self._h, first, len(a), _ptr(buf)), "lb_balance_table_put")
+        return self.balance_table_size()
+
+    def balance_table_size(self) -> int:
+        n = ctypes.c_uint32(0)
+        self._check(self.lib.lb_balance_table_size(self._h, ctypes.byref(n)), "lb_balance_table_size")
+        return int(n.value)
+
+    def balance_table_read(self, first: int, n: int) -> np.ndarray:
+        out = np.zeros(max(n, 1), np.uint8)
+        self._check(self.lib.lb_balance_table_read(self._h, first, n, _ptr(out)), "lb_balance_table_read")
+        return out[:n]
+
+    def sample_by_balance(self, seeds: Sequence[bytes], count: int, active_indices, max_increment: int,
+                          max_candidates: int, store_list: int = LB_NO_LIST, out=None) -> SampleResult:
+        """lb_sample_by_balance: per seed, the first `count` candidates of the shuffled walk over
+        active_indices that the balance test accepts, within max_candidates.  store_list: the
+        index list a lone seed's filled result replaces, on the device.  out: the caller's own
+        (indices[n_seeds * count], found[n_seeds], tried[n_seeds]) uint32 arrays to write into."""
+        seeds = [bytes(s) for s in seeds]
+        if any(len(s) != 32 for s in seeds):
+            raise ValueError("seeds must be 32 bytes each")
+        seed_a = _u8(b"".join(seeds)) if seeds else np.zeros(1, np.uint8)
+        a = np.ascontiguousarray(active_indices, dtype=np.uint32)
+        buf = a if len(a) else np.zeros(1, np.uint32)
+        ns = len(seeds)
+        if out is None:
+            out = (np.zeros(max(ns * count, 1), np.uint32), np.zeros(max(ns, 1), np.uint32),
+                   np.zeros(max(ns, 1), np.uint32))
+        idx, found, tried = out
+        if any(x.dtype != np.uint32 or not x.flags.c_contiguous for x in out) or len(idx) < ns * count or \
+                len(found) < ns or len(tried) < ns:
+            raise ValueError("out: contiguous uint32 arrays of n_seeds * count, n_seeds and n_seeds entries")
+        rc = self.lib.lb_sample_by_balance(self._h, ns, _ptr(seed_a), count, len(a), _ptr(buf), max_increment,
+                                           max_candidates, store_list, _ptr(idx), _ptr(found), _ptr(tried))
+        self._check(rc, "lb_sample_by_balance")
+        return SampleResult(idx[:ns * count].reshape(ns, count), found[:ns], tried[:ns])
+
+    def aggregate_pubkeys_list(self, list_id: int, first: int, n: int) -> bytes:
+        """lb_aggregate_pubkeys_list: the sum of the table's keys at list[first : first + n]."""
+        out = np.zeros(96, np.uint8)
+        st = np.zeros(1, np.uint8)
+        rc = self.lib.lb_aggregate_pubkeys_list(self._h, list_id, first, n, _ptr(out), _ptr(st))
+        self._check(rc, "lb_aggregate_pubkeys_list")
+        if st[0] != 0:
+            raise BadPubkeyError(SET_STATUS_NAMES.get(int(st[0]), str(st[0])))
+        return out.tobytes()
 
     def wait_call(self, pc: "PendingCall") -> VerifyResult:
         st = _Stats()

@@ -29,6 +29,7 @@ from __future__ import annotations
 import asyncio
 import concurrent.futures
 import enum
+import hashlib
 import os
 import threading
 import time
@@ -41,6 +42,7 @@ import numpy as np
 from . import metrics as M
 from .native import (LB_KEYS_BITS, LB_KEYS_DIRECT, LB_KEYS_SLICE, LB_PK_ROW_FLAG, PendingSameMessage, LB_REQ_BAD_PUBKEY, LB_REQ_EMPTY_AGGREGATE, BadPubkeyError, Device, EmptyAggregateError,
                      pack_blobs)
+from .native import LB_SAMPLE_MAX_CANDIDATES, LB_SAMPLE_NONE
 
 MAX_SIGNATURE_SETS_PER_JOB = 128      # index.ts:57
 MAX_BUFFERED_SIGS = 32                # index.ts:66
@@ -513,6 +515,40 @@ class DeviceBackend:
         """Store validator indices as given (a sync committee's) as index list `list_id`."""
         return self._put("call", lambda cs: self.dev.index_list_put(list_id, indices)).result()
 
+    def sync_balances(self, increments, first: int = 0) -> int:
+        """EffectiveBalanceIncrements (cache/effectiveBalanceIncrements.ts:8) to the device's
+        balance table: overwrite or append from validator index `first`; returns its size."""
+        return self._put("call", lambda cs: self.dev.balance_table_put(increments, first)).result()
+
+    def compute_proposers(self, epoch_seed: bytes, start_slot: int, active_indices, slots: int = 32,
+                          max_increment: int = 32) -> List[int]:
+        """computeProposers (util/seed.ts:22-80) on the GPU: the proposer of each of `slots` slots
+        from start_slot, sampled by balance from the device's table; -1 where a slot found none
+        among its len(active_indices) candidates."""
+        seeds = [hashlib.sha256(bytes(epoch_seed) + int(start_slot + i).to_bytes(8, "little")).digest()
+                 for i in range(slots)]  # seed.ts:34
+
+        def run(cs):
+            r = self.dev.sample_by_balance(seeds, 1, active_indices, max_increment, len(active_indices))
+            return [-1 if int(v) == LB_SAMPLE_NONE else int(v) for v in r.indices[:, 0]]
+        return self._put("call", run).result()
+
+    def sync_committee(self, list_id: int, active_indices, seed: bytes, size: int = 512, max_increment: int = 32,
+                       max_candidates: int = LB_SAMPLE_MAX_CANDIDATES) -> Tuple[np.ndarray, bytes]:
+        """getNextSyncCommitteeIndices (util/seed.ts:92-126) and getNextSyncCommittee's
+        aggregatePubkey (util/syncCommittee.ts:21-38) on the GPU: index list `list_id` becomes
+        the committee's `size` validator indices (sync aggregates are then bits_set over it),
+        which are returned with the 96-byte aggregate of their keys.  Raises when the committee
+        did not fill within max_candidates (the reference would loop)."""
+        def run(cs):
+            r = self.dev.sample_by_balance([seed], size, active_indices, max_increment, max_candidates,
+                                           store_list=list_id)
+            if int(r.found[0]) != size:
+                raise RuntimeError("sync committee not filled: %d of %d accepted among %d candidates"
+                                   % (int(r.found[0]), size, max_candidates))
+            return r.indices[0].copy(), self.dev.aggregate_pubkeys_list(list_id, 0, size)
+        return self._put("call", run).result()
+
     def close(self) -> None:
         """Finish every queued and in-flight call, then release the device
         (from the submission thread, after its last call -- never under one)."""
@@ -580,6 +616,25 @@ class BlsGpuVerifier:
     def put_index_list(self, list_id: int, indices) -> None:
         for b in self.backends:
             b.put_index_list(list_id, indices)
+
+    def sync_balances(self, increments, first: int = 0) -> int:
+        """Effective-balance increments to every GPU's balance table; returns its size."""
+        sizes = [b.sync_balances(increments, first) for b in self.backends]
+        if len(set(sizes)) != 1:
+            raise RuntimeError(f"balance tables out of sync across devices: {sizes}")
+        return sizes[0]
+
+    def compute_proposers(self, epoch_seed: bytes, start_slot: int, active_indices, slots: int = 32,
+                          max_increment: int = 32) -> List[int]:
+        """An epoch's proposers, sampled on the first GPU (every GPU holds the same table)."""
+        return self.backends[0].compute_proposers(epoch_seed, start_slot, active_indices, slots, max_increment)
+
+    def sync_committee(self, list_id: int, active_indices, seed: bytes, size: int = 512, max_increment: int = 32,
+                       max_candidates: int = LB_SAMPLE_MAX_CANDIDATES) -> Tuple[np.ndarray, bytes]:
+        """The sync committee sampled on, and kept by, every GPU as index list `list_id`."""
+        outs = [b.sync_committee(list_id, active_indices, seed, size, max_increment, max_candidates)
+                for b in self.backends]
+        return outs[0]
 
     # ---- IBlsVerifier --------------------------------------------------------------
     def can_accept_work(self) -> bool:
