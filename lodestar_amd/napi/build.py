@@ -21,19 +21,25 @@ def available() -> bool:
     return os.path.exists(os.path.join(NODE_INCLUDE, "node_api.h")) and shutil.which("g++") is not None
 
 
-def build(force: bool = False, verbose: bool = False) -> str:
+def build(force: bool = False, verbose: bool = False, out: str | None = None, lib_dir: str | None = None) -> str:
+    """Build the addon.  By default into this directory against the package's library; with
+    `out` / `lib_dir`, the same sources and flags into `out` against the liblodestar_bls.so in
+    `lib_dir` (the tests link a stand-in library this way)."""
     src = os.path.join(HERE, "addon.cc")
-    deps = [src, os.path.join(ROOT, "include", "lodestar_bls.h"), os.path.join(PKG, "liblodestar_bls.so")]
-    if not force and os.path.exists(OUT) and os.path.getmtime(OUT) >= max(os.path.getmtime(p) for p in deps):
-        return OUT
+    out = out or OUT
+    rpath = os.path.abspath(lib_dir) if lib_dir else "$ORIGIN/.."
+    lib_dir = lib_dir or PKG
+    deps = [src, os.path.join(ROOT, "include", "lodestar_bls.h"), os.path.join(lib_dir, "liblodestar_bls.so")]
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(p) for p in deps):
+        return out
     cmd = ["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
            "-DNODE_GYP_MODULE_NAME=lodestar_bls", f"-I{NODE_INCLUDE}", f"-I{os.path.join(ROOT, 'include')}",
-           src, "-o", OUT + ".tmp", f"-L{PKG}", "-llodestar_bls", "-Wl,-rpath,$ORIGIN/..", "-pthread"]
+           src, "-o", out + ".tmp", f"-L{lib_dir}", "-llodestar_bls", f"-Wl,-rpath,{rpath}", "-pthread"]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    os.replace(OUT + ".tmp", OUT)
-    return OUT
+    os.replace(out + ".tmp", out)
+    return out
 
 
 if __name__ == "__main__":
