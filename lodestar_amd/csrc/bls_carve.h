@@ -31,6 +31,19 @@ inline size_t carve_take(size_t& end, size_t bytes, bool present = true) {
   return off;
 }
 
+// The capacity a device array owned by the context (DevArray, bls_host.hip) takes to hold `need`
+// elements when it has `cap`: `cap` while that is enough.  A table (`doubling`: the pubkey and
+// balance tables, which grow by appends) at least doubles, within kDevArrayMax entries; a list
+// takes exactly `need`.  Either takes at least `floor`, and never less than `need`.
+static constexpr uint32_t kDevArrayMax = 0x7fffffffu;
+inline uint32_t dev_array_cap(uint32_t cap, uint32_t need, uint32_t floor, bool doubling) {
+  if (need <= cap) return cap;
+  uint64_t c = doubling ? (uint64_t)cap * 2 : need;
+  if (c > kDevArrayMax) c = kDevArrayMax;
+  if (c < floor) c = floor;
+  return c < need ? need : (uint32_t)c;
+}
+
 enum CarveKind : uint8_t { CARVE_IN, CARVE_SCRATCH, CARVE_OUT };
 
 struct CarveBuf {

@@ -225,22 +225,43 @@ struct TicketStats {
   float wall_ms = 0.f;
 };
 
-// Blob KZG verification (lb_kzg_*): the loaded setup, the roots-of-unity table and a
-// workspace of its own (LB_KZG_MAX_BLOBS blobs), apart from the slots' workspaces.
+// A device array the context owns for its lifetime: d[0, n) of cap entries.  reserve() makes
+// room for `need` entries by the array's policy (dev_array_cap, bls_carve.h), keeps the first
+// `keep` (n = keep once the array has moved) and names the array in the context's error when
+// the device has no room.  The calls in flight, which may read the array, are the caller's to
+// retire first (helper_slot), and the copies are the caller's to wait for.
+struct lb_ctx;
+template <class T>
+struct DevArray {
+  const char* const name;
+  const uint32_t floor;
+  const bool doubling;
+  T* d = nullptr;
+  uint32_t n = 0, cap = 0;
+  explicit DevArray(const char* name_, uint32_t floor_ = 0, bool doubling_ = false)
+      : name(name_), floor(floor_), doubling(doubling_) {}
+  DevArray(const DevArray&) = delete;
+  DevArray& operator=(const DevArray&) = delete;
+  ~DevArray() {
+    if (d) (void)hipFree(d);
+  }
+  int reserve(lb_ctx* ctx, uint32_t need, uint32_t keep);
+  // d[first, first + count) from / to host memory, on ctx->stream
+  int upload(lb_ctx* ctx, uint32_t first, const T* src, uint32_t count);
+  int download(lb_ctx* ctx, uint32_t first, T* dst, uint32_t count) const;
+};
+
+// Blob KZG (lb_kzg_*): what persists across calls -- the roots-of-unity table and the two
+// halves of the loaded setup.  A call's own buffers are carved from slot 0's slab (HelperCall).
 struct KzgState {
   bool loaded = false;
-  fr* d_roots = nullptr;     // roots[i] = omega^brp(i), Montgomery form (k_kzg_roots)
-  g2a* d_neg_tau = nullptr;  // [0]: -[tau]_2 of the loaded setup, [1]: a candidate being checked
-  char* d_ws = nullptr;
-  size_t ws_cap = 0;
-  hipEvent_t ev[6] = {};
+  DevArray<fr> roots{"KZG roots"};     // roots[i] = omega^brp(i), Montgomery form (k_kzg_roots); n: built
+  DevArray<g2a> neg_tau{"KZG setup"};  // [0]: -[tau]_2 of the loaded setup, [1]: a candidate being checked
   // commitments and proofs (k_kzg_msm.hip): the window table of the Lagrange G1 setup,
   // T[j][i] = [2^(8j)] L[i]; [g1_cur] is the loaded one, the other takes a candidate
   bool g1_loaded = false;
-  g1a* d_g1_tab[2] = {nullptr, nullptr};
+  DevArray<g1a> g1_tab[2] = {DevArray<g1a>{"KZG G1 table"}, DevArray<g1a>{"KZG G1 table"}};
   int g1_cur = 0;
-  char* d_msm_ws = nullptr;  // the MSM's workspace (LB_KZG_MSM_GROUP jobs), allocated by the first load
-  size_t msm_cap = 0;
 };
 
 struct lb_ctx {
@@ -280,20 +301,21 @@ struct lb_ctx {
   // lb_set_same_message_mode; ccfg.sm_randomized at lb_create
   uint32_t sm_mode = LB_SM_PLAIN;
   // device-resident pubkey table (index2pubkey mirror, lb_pubkey_table_*)
-  g1a* d_table = nullptr;
-  uint32_t table_n = 0, table_cap = 0;
+  DevArray<g1a> table{"pubkey table", 4096, true};
   // device-resident index lists (lb_index_list_*): shufflings and sync committees that the sets
-  // of a lb_verify_requests_keys* call name their keys from (k_lists.hip)
-  struct IndexList {
-    uint32_t* d = nullptr;
-    uint32_t n = 0, cap = 0;
+  // of a lb_verify_requests_keys* call name their keys from (k_lists.hip); n stays 0 until the
+  // kernels or the copy that fill a list are known to have run
+  struct IndexList : DevArray<uint32_t> {
+    IndexList() : DevArray("index list", 1024) {}
   } lists[LB_INDEX_LISTS];
-  hipEvent_t list_ev[2] = {};  // lb_index_list_shuffle's and lb_sample_by_balance's stage time
   // device-resident balance table (EffectiveBalanceIncrements mirror, lb_balance_table_*): one
   // byte per validator, what lb_sample_by_balance weighs its candidates by (k_sample.hip)
-  uint8_t* d_bal = nullptr;
-  uint32_t bal_n = 0, bal_cap = 0;
-  // timing of the last completed verify call
+  DevArray<uint8_t> bal{"balance table", 4096, true};
+  // the stage clock of the synchronous helper calls (HelperCall::stage): stage i of a call spans
+  // helper_ev[i] .. helper_ev[i + 1]
+  static constexpr int kHelperStages = 4;
+  hipEvent_t helper_ev[kHelperStages + 1] = {};
+  // timing of the last completed verify call, or of the last helper call that timed its stages
   int n_stages = 0;
   float stage_ms[Slot::kMaxStages] = {};
   const char* stage_name[Slot::kMaxStages] = {};
@@ -313,15 +335,13 @@ struct lb_ctx {
   size_t aux_cap = 0;
   // latency path: the round programs in device memory (uploaded on first use);
   // calls of at most cfg.lp_max_sets sets run it instead of the throughput pipeline
-  uint32_t* d_lp = nullptr;
+  DevArray<uint32_t> d_lp{"latency-path programs"};
   int last_call_streams = 0;  // streams of the last submitted verify call (begin_call)
   unsigned long long lp_clk[4] = {};  // clock stamps of the last retired latency-path call
 };
 
-namespace {
-
 #define LB_HIP(call)                                                                   \
-  do {                                                                                 \
+  do {                                                                               \
     hipError_t e_ = (call);                                                            \
     if (e_ != hipSuccess) {                                                            \
       ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                    \
@@ -334,6 +354,44 @@ namespace {
     int rc_ = (x);                \
     if (rc_ != LB_OK) return rc_; \
   } while (0)
+
+template <class T>
+int DevArray<T>::reserve(lb_ctx* ctx, uint32_t need, uint32_t keep) {
+  if (need <= cap) return LB_OK;
+  const uint32_t grown = dev_array_cap(cap, need, floor, doubling);
+  T* fresh = nullptr;
+  if (hipMalloc(&fresh, sizeof(T) * (size_t)grown) != hipSuccess) {
+    ctx->err = std::string("hipMalloc ") + name + " failed";
+    return LB_ERR_OUT_OF_MEMORY;
+  }
+  if (d) {  // (the old array stays as it is when the copy fails)
+    hipError_t e = keep ? hipMemcpyAsync(fresh, d, sizeof(T) * (size_t)keep, hipMemcpyDeviceToDevice, ctx->stream)
+                        : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+      (void)hipFree(fresh);
+      ctx->err = std::string("moving the ") + name + ": " + hipGetErrorString(e);
+      return LB_ERR_DEVICE;
+    }
+    LB_HIP(hipFree(d));
+  }
+  d = fresh;
+  cap = grown;
+  n = keep;
+  return LB_OK;
+}
+template <class T>
+int DevArray<T>::upload(lb_ctx* ctx, uint32_t first, const T* src, uint32_t count) {
+  LB_HIP(hipMemcpyAsync(d + first, src, sizeof(T) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+  return LB_OK;
+}
+template <class T>
+int DevArray<T>::download(lb_ctx* ctx, uint32_t first, T* dst, uint32_t count) const {
+  LB_HIP(hipMemcpyAsync(dst, d + first, sizeof(T) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
+  return LB_OK;
+}
+
+namespace {
 
 inline uint32_t blocks_for(uint32_t n, uint32_t tpb = TPB) { return (n + tpb - 1) / tpb; }
 
@@ -454,7 +512,7 @@ int run_lp(lb_ctx* ctx, Slot& sl, uint32_t n_req, uint32_t n_sets, const uint32_
     LB_HIP(hipMemsetAsync(d_req_err, 0, n_req, sl.st[0]));
     return LB_OK;
   }
-  const PkSource src{d_pks, d_pk_idx, ctx->d_table, ctx->table_n};
+  const PkSource src{d_pks, d_pk_idx, ctx->table.d, ctx->table.n};
   LB_STAGE("pubkeys", 0, k_pubkeys_single, blocks_for(n_sets), TPB, n_sets, src, d_pk_off, d_pk, d_pk_st);
   if (d_pk_off)
     LB_STAGE("pubkeys_agg", 0, k_pubkeys_agg, n_sets < 16384u ? n_sets : 16384u, TPB, n_sets, src, d_pk_off, d_pk,
@@ -463,10 +521,10 @@ int run_lp(lb_ctx* ctx, Slot& sl, uint32_t n_req, uint32_t n_sets, const uint32_
            (const g1j*)d_pk, d_seed, d_in16, d_fl, d_sig_st, d_setreq, d_valid, d_req_err, d_cnt,
            (uint32_t)LB_LP_TREE_LEVELS * ns, d_clk);
   LpCall c;
-  c.prog_single = ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_SET_SINGLE].off;
-  c.prog_batch = ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_SET_BATCH].off;
-  c.prog_mul = ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_MUL].off;
-  c.prog_final = ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_FINAL].off;
+  c.prog_single = ctx->d_lp.d + LB_LP_PROGS[LB_LP_PROG_SET_SINGLE].off;
+  c.prog_batch = ctx->d_lp.d + LB_LP_PROGS[LB_LP_PROG_SET_BATCH].off;
+  c.prog_mul = ctx->d_lp.d + LB_LP_PROGS[LB_LP_PROG_MUL].off;
+  c.prog_final = ctx->d_lp.d + LB_LP_PROGS[LB_LP_PROG_FINAL].off;
   c.req_off = d_req_off;
   c.set_req = d_setreq;
   c.in16 = d_in16;
@@ -523,7 +581,7 @@ int run_tails(lb_ctx* ctx, Slot& sl) {
     if (p.d_rt_in) {
       LB_ENQUEUE(sl.st[0], k_rtail_prep, (p.n_req * LB_RTAIL_NIN + 255) / 256, 256, p.n_req, (const fp12*)p.d_F,
                  (const g2a*)p.d_S, p.d_rt_in, p.d_rt_fl);
-      LB_STAGE("rtail", 0, k_lp_rtail, p.n_req, LB_LP_TPB, ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_RTAIL].off, p.n_req,
+      LB_STAGE("rtail", 0, k_lp_rtail, p.n_req, LB_LP_TPB, ctx->d_lp.d + LB_LP_PROGS[LB_LP_PROG_RTAIL].off, p.n_req,
                (const uint32_t*)p.d_rt_in, (const uint32_t*)p.d_rt_fl, (const uint8_t*)p.d_bad, p.d_valid,
                (const uint8_t*)p.d_mflag);
     } else {
@@ -688,7 +746,7 @@ static decltype(&k_miller_acc<64>) miller_acc_kernel(const PipePlan& p) {
   return p.acc_lpr == 16 ? k_miller_acc<16> : p.acc_lpr == 32 ? k_miller_acc<32> : k_miller_acc<64>;
 }
 
-static const uint32_t* lp_prog(const lb_ctx* ctx, int prog) { return ctx->d_lp + LB_LP_PROGS[prog].off; }
+static const uint32_t* lp_prog(const lb_ctx* ctx, int prog) { return ctx->d_lp.d + LB_LP_PROGS[prog].off; }
 
 // ---- the stages, in the order run_pipeline enqueues them ------------------------------------
 // Each tests plan fields only.  Stream 0 carries the call's spine, stream 1 the hash and the lines.
@@ -736,7 +794,7 @@ static int enqueue_row_order(lb_ctx* ctx, Slot& sl, const PipePlan& p, const Pip
 static int enqueue_pubkeys(lb_ctx* ctx, Slot& sl, const PipePlan& p, const PipeBufs& b) {
   const uint32_t n_sets = p.n_sets;
   if (!n_sets) return LB_OK;
-  const PkSource src{b.pks, b.pk_idx, ctx->d_table, ctx->table_n};
+  const PkSource src{b.pks, b.pk_idx, ctx->table.d, ctx->table.n};
   LB_STAGE("pubkeys", 0, k_pubkeys_single, blocks_for(n_sets), TPB, n_sets, src, b.pk_off, b.pk, b.pk_st);
   if (b.pk_off)
     // one wave per set, grid-stride: enough waves that every aggregate of a
@@ -1342,14 +1400,9 @@ int helper_slot(lb_ctx* ctx) {
 
 // latency path: upload the round programs once (2.6 MB)
 int lp_ensure(lb_ctx* ctx) {
-  if (ctx->d_lp) return LB_OK;
-  const size_t bytes = (size_t)LB_LP_BLOB_WORDS * 4;
-  if (hipMalloc(&ctx->d_lp, bytes) != hipSuccess) {
-    ctx->d_lp = nullptr;
-    ctx->err = "hipMalloc latency-path programs failed";
-    return LB_ERR_OUT_OF_MEMORY;
-  }
-  LB_HIP(hipMemcpy(ctx->d_lp, lb_lp_blob, bytes, hipMemcpyHostToDevice));
+  if (ctx->d_lp.d) return LB_OK;
+  LB_TRY(ctx->d_lp.reserve(ctx, LB_LP_BLOB_WORDS, 0));
+  LB_HIP(hipMemcpy(ctx->d_lp.d, lb_lp_blob, (size_t)LB_LP_BLOB_WORDS * 4, hipMemcpyHostToDevice));
   return LB_OK;
 }
 
@@ -1469,6 +1522,7 @@ static int create_ctx(int device, lb_ctx** out_ctx, bool lane) {
     if (ok) sl.h_stats[0] = sl.h_stats[1] = 0;
   }
   ctx->stream = ctx->slots[0].st[0];
+  for (hipEvent_t& e : ctx->helper_ev) ok = ok && hipEventCreate(&e) == hipSuccess;
   // the host combine's one-wave final exponentiation must not queue behind the
   // calls in flight (their 1-wave/SIMD kernels fill every SIMD): highest priority
   ok = ok && hipStreamCreateWithPriority(&ctx->aux_stream, hipStreamNonBlocking, prio_greatest) == hipSuccess;
@@ -1542,12 +1596,8 @@ int lb_destroy(lb_ctx* ctx) {
     if (sl.h_clk) (void)hipHostFree(sl.h_clk);
     for (int i = 0; i < n_own; i++) (void)hipStreamDestroy(own[i]);
   }
-  if (ctx->d_table) (void)hipFree(ctx->d_table);
-  for (lb_ctx::IndexList& l : ctx->lists)
-    if (l.d) (void)hipFree(l.d);
-  for (hipEvent_t e : ctx->list_ev)
+  for (hipEvent_t e : ctx->helper_ev)
     if (e) (void)hipEventDestroy(e);
-  if (ctx->d_bal) (void)hipFree(ctx->d_bal);
   if (ctx->aux_stream) {
     (void)hipStreamSynchronize(ctx->aux_stream);
     (void)hipStreamDestroy(ctx->aux_stream);
@@ -1558,22 +1608,13 @@ int lb_destroy(lb_ctx* ctx) {
   }
   if (ctx->d_aux) (void)hipFree(ctx->d_aux);
   if (ctx->h_aux) (void)hipHostFree(ctx->h_aux);
-  if (ctx->d_lp) (void)hipFree(ctx->d_lp);
-  if (ctx->kzg.d_roots) (void)hipFree(ctx->kzg.d_roots);
-  if (ctx->kzg.d_neg_tau) (void)hipFree(ctx->kzg.d_neg_tau);
-  if (ctx->kzg.d_ws) (void)hipFree(ctx->kzg.d_ws);
-  if (ctx->kzg.d_msm_ws) (void)hipFree(ctx->kzg.d_msm_ws);
-  for (g1a* t : ctx->kzg.d_g1_tab)
-    if (t) (void)hipFree(t);
-  for (hipEvent_t e : ctx->kzg.ev)
-    if (e) (void)hipEventDestroy(e);
   {
     std::lock_guard<std::mutex> g(g_q_mu);
     g_q.plain -= ctx->plan.q_plain;
     g_q.high -= ctx->plan.q_high;
     g_q.masked -= ctx->plan.q_masked;
   }
-  delete ctx;
+  delete ctx;  // (its DevArrays free their memory here, on the device selected above)
   return LB_OK;
 }
 
@@ -2170,7 +2211,7 @@ int lb_gt_check(lb_ctx* ctx, uint32_t n, const uint8_t* partials576, int32_t* ou
     uint32_t* d_rec = reinterpret_cast<uint32_t*>(ctx->d_aux + 256 + (((size_t)n * LB_GT_BYTES + 255) & ~(size_t)255));
     LB_ENQUEUE(ctx->aux_stream, k_gt_prod, 1, TPB, n, (const uint8_t*)d_in, d_rec, d_out);
     LB_ENQUEUE(ctx->aux_stream, k_lp_final_lane, 1, LB_LP_TPB,
-               (const uint32_t*)(ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_FINAL_LANE].off), (const uint32_t*)d_rec, d_out);
+               (const uint32_t*)(ctx->d_lp.d + LB_LP_PROGS[LB_LP_PROG_FINAL_LANE].off), (const uint32_t*)d_rec, d_out);
   } else {
     LB_ENQUEUE(ctx->aux_stream, k_gt_check, 1, TPB, n, (const uint8_t*)d_in, d_out);
   }
@@ -2326,10 +2367,36 @@ int lb_verify_requests_keys_priority_async(lb_ctx* ctx, const lb_request_batch* 
 // A synchronous helper call on the idle slot 0: the call declares its buffers (bls_carve.h),
 // begin() selects the device, retires the calls in flight, sizes and carves slot 0's slab from
 // the list and uploads the inputs on ctx->stream; the call launches; end() downloads the
-// outputs and synchronises once.
-struct HelperCall : Carve<16> {
+// outputs and synchronises once.  A call that wants its time in lb_last_stage_times names its
+// stages as it launches: stage() closes the stage before it and opens the next on ctx->stream,
+// stage_end() closes the last (end() does, ahead of the downloads, when the call has not), and
+// end() publishes them.  The first stage() clears the stages published before, whether or not
+// ccfg.stage_events has any event recorded; a call that names no stage leaves them alone.
+// Stages follow one another without a gap.  A call may launch again after end() and call it a
+// second time for what those launches wrote (kzg_finish_verify).
+// (The longest list is kzg_prove's: 16 buffers.)
+struct HelperCall : Carve<24> {
   lb_ctx* ctx;
+  const char* stage_name[lb_ctx::kHelperStages] = {};
+  int n_staged = 0;
+  bool stage_open = false;
   explicit HelperCall(lb_ctx* c) : ctx(c) {}
+  int stage(const char* name) {
+    if (n_staged == lb_ctx::kHelperStages) {
+      ctx->err = "more stages than the helper calls' clock has events for";
+      return LB_ERR_INVALID_ARGUMENT;
+    }
+    if (n_staged == 0) ctx->n_stages = 0;
+    if (ctx->ccfg.stage_events) LB_HIP(hipEventRecord(ctx->helper_ev[n_staged], ctx->stream));
+    stage_name[n_staged++] = name;
+    stage_open = true;
+    return LB_OK;
+  }
+  int stage_end() {
+    if (stage_open && ctx->ccfg.stage_events) LB_HIP(hipEventRecord(ctx->helper_ev[n_staged], ctx->stream));
+    stage_open = false;
+    return LB_OK;
+  }
   int begin() {
     LB_HIP(hipSetDevice(ctx->device));
     LB_TRY(helper_slot(ctx));
@@ -2346,11 +2413,19 @@ struct HelperCall : Carve<16> {
     return LB_OK;
   }
   int end() {
+    LB_TRY(stage_end());
     const Slot& sl = ctx->slots[0];
     for (int i = 0; i < n; i++)
       if (buf[i].kind == CARVE_OUT && buf[i].bytes && buf[i].dst)
         LB_HIP(hipMemcpyAsync(buf[i].dst, sl.d_ws + buf[i].off, buf[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
     LB_HIP(hipStreamSynchronize(ctx->stream));
+    if (!ctx->ccfg.stage_events) return LB_OK;
+    for (int i = 0; i < n_staged; i++) {
+      LB_HIP(hipEventElapsedTime(&ctx->stage_ms[i], ctx->helper_ev[i], ctx->helper_ev[i + 1]));
+      ctx->stage_name[i] = stage_name[i];
+      ctx->stage_ops[i] = 0;
+    }
+    if (n_staged) ctx->n_stages = n_staged;
     return LB_OK;
   }
 };
@@ -2401,8 +2476,8 @@ static int aggregate_pubkeys(lb_ctx* ctx, uint32_t n, const uint8_t* pks, const 
   auto d_st = c.out(&st, 1);
   LB_TRY(c.begin());
   const bool by_index = indices || dev_indices;
-  const PkSource src{d_p, dev_indices ? dev_indices : (const uint32_t*)d_idx, by_index ? ctx->d_table : nullptr,
-                     by_index ? ctx->table_n : 0};
+  const PkSource src{d_p, dev_indices ? dev_indices : (const uint32_t*)d_idx, by_index ? ctx->table.d : nullptr,
+                     by_index ? ctx->table.n : 0};
   LB_LAUNCH(k_pubkeys_single, 1, TPB, 1u, src, d_off, d_pk, d_st);
   LB_LAUNCH(k_pubkeys_agg, 1, TPB, 1u, src, d_off, d_pk, d_st);
   LB_LAUNCH(k_g1_serialize, 1, TPB, 1u, (const g1j*)d_pk, d_out);
@@ -2439,30 +2514,14 @@ int lb_pubkey_table_append(lb_ctx* ctx, uint32_t n, const uint8_t* pks, uint32_t
   if (!ctx || (n && !pks) || (pk_len != 48 && pk_len != 96)) return LB_ERR_INVALID_ARGUMENT;
   if (out_bad_index) *out_bad_index = -1;
   if (n == 0) return LB_OK;
-  if ((uint64_t)ctx->table_n + n > 0x7fffffffu) {
+  if ((uint64_t)ctx->table.n + n > 0x7fffffffu) {
     ctx->err = "pubkey table full";
     return LB_ERR_INVALID_ARGUMENT;
   }
   LB_HIP(hipSetDevice(ctx->device));
   LB_TRY(helper_slot(ctx));  // calls in flight read the table
-  const uint32_t need = ctx->table_n + n;
-  if (need > ctx->table_cap) {
-    uint64_t cap = (uint64_t)ctx->table_cap * 2;
-    if (cap < need) cap = need;
-    if (cap < 4096) cap = 4096;
-    if (cap > 0x7fffffffu) cap = 0x7fffffffu;
-    g1a* d = nullptr;
-    if (hipMalloc(&d, sizeof(g1a) * cap) != hipSuccess) {
-      ctx->err = "hipMalloc pubkey table failed";
-      return LB_ERR_OUT_OF_MEMORY;
-    }
-    if (ctx->table_n)
-      LB_HIP(hipMemcpyAsync(d, ctx->d_table, sizeof(g1a) * ctx->table_n, hipMemcpyDeviceToDevice, ctx->stream));
-    LB_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_table) LB_HIP(hipFree(ctx->d_table));
-    ctx->d_table = d;
-    ctx->table_cap = (uint32_t)cap;
-  }
+  const uint32_t need = ctx->table.n + n;
+  LB_TRY(ctx->table.reserve(ctx, need, ctx->table.n));
   // decode straight into the table tail, in chunks that bound the staging workspace;
   // table_n only advances once every key decoded
   const uint32_t chunk = 1u << 20;
@@ -2474,7 +2533,7 @@ int lb_pubkey_table_append(lb_ctx* ctx, uint32_t n, const uint8_t* pks, uint32_t
     auto d_in = c.in(pks + (size_t)first * pk_len, (size_t)m * pk_len);
     auto d_st = c.out(st.data(), m);
     LB_TRY(c.begin());
-    LB_LAUNCH(k_table_decode, blocks_for(m), TPB, m, d_in, pk_len, ctx->d_table + ctx->table_n + first, d_st);
+    LB_LAUNCH(k_table_decode, blocks_for(m), TPB, m, d_in, pk_len, ctx->table.d + ctx->table.n + first, d_st);
     LB_TRY(c.end());
     for (uint32_t i = 0; i < m; i++)
       if (st[i] != LB_ST_OK) {
@@ -2483,31 +2542,31 @@ int lb_pubkey_table_append(lb_ctx* ctx, uint32_t n, const uint8_t* pks, uint32_t
         return LB_ERR_INVALID_ARGUMENT;
       }
   }
-  ctx->table_n = need;
+  ctx->table.n = need;
   return LB_OK;
 }
 
 int lb_pubkey_table_size(const lb_ctx* ctx, uint32_t* out_n) {
   if (!ctx || !out_n) return LB_ERR_INVALID_ARGUMENT;
-  *out_n = ctx->table_n;
+  *out_n = ctx->table.n;
   return LB_OK;
 }
 
 int lb_pubkey_table_truncate(lb_ctx* ctx, uint32_t n) {
-  if (!ctx || n > ctx->table_n) return LB_ERR_INVALID_ARGUMENT;
+  if (!ctx || n > ctx->table.n) return LB_ERR_INVALID_ARGUMENT;
   LB_HIP(hipSetDevice(ctx->device));
   LB_TRY(helper_slot(ctx));
-  ctx->table_n = n;
+  ctx->table.n = n;
   return LB_OK;
 }
 
 int lb_pubkey_table_read(lb_ctx* ctx, uint32_t first, uint32_t n, uint8_t* out96) {
-  if (!ctx || (n && !out96) || (uint64_t)first + n > ctx->table_n) return LB_ERR_INVALID_ARGUMENT;
+  if (!ctx || (n && !out96) || (uint64_t)first + n > ctx->table.n) return LB_ERR_INVALID_ARGUMENT;
   if (n == 0) return LB_OK;
   HelperCall c(ctx);
   auto d_out = c.out(out96, (size_t)n * 96);
   LB_TRY(c.begin());
-  LB_LAUNCH(k_g1a_serialize, blocks_for(n), TPB, n, (const g1a*)(ctx->d_table + first), d_out);
+  LB_LAUNCH(k_g1a_serialize, blocks_for(n), TPB, n, (const g1a*)(ctx->table.d + first), d_out);
   return c.end();
 }
 
@@ -2522,30 +2581,15 @@ int lb_aggregate_pubkeys_indexed(lb_ctx* ctx, uint32_t n, const uint32_t* indice
 }
 
 // ---- device-resident index lists (shufflings, sync committees) -------------------
-// Room for n entries in list L; the calls in flight, which may read it, have retired
-static int list_reserve(lb_ctx* ctx, lb_ctx::IndexList& L, uint32_t n) {
-  if (n <= L.cap) return LB_OK;
-  const uint32_t cap = n < 1024 ? 1024 : n;
-  uint32_t* d = nullptr;
-  if (hipMalloc(&d, sizeof(uint32_t) * (size_t)cap) != hipSuccess) {
-    ctx->err = "hipMalloc index list failed";
-    return LB_ERR_OUT_OF_MEMORY;
-  }
-  if (L.d) LB_HIP(hipFree(L.d));
-  L.d = d;
-  L.cap = cap;
-  L.n = 0;
-  return LB_OK;
-}
-
+// (a list that is written takes all new contents: reserve keeps none of the old)
 int lb_index_list_put(lb_ctx* ctx, uint32_t list, uint32_t n, const uint32_t* indices) {
   if (!ctx || list >= LB_INDEX_LISTS || (n && !indices)) return LB_ERR_INVALID_ARGUMENT;
   LB_HIP(hipSetDevice(ctx->device));
   LB_TRY(helper_slot(ctx));  // calls in flight read the lists
   lb_ctx::IndexList& L = ctx->lists[list];
   if (n) {
-    LB_TRY(list_reserve(ctx, L, n));
-    LB_HIP(hipMemcpyAsync(L.d, indices, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    LB_TRY(L.reserve(ctx, n, 0));
+    LB_TRY(L.upload(ctx, 0, indices, n));
     LB_HIP(hipStreamSynchronize(ctx->stream));
   }
   L.n = n;
@@ -2559,18 +2603,12 @@ int lb_index_list_shuffle(lb_ctx* ctx, uint32_t list, uint32_t n, const uint32_t
     ctx->err = "lb_index_list_shuffle: more than LB_SHUFFLE_MAX indices";
     return LB_ERR_INVALID_ARGUMENT;
   }
-  ctx->n_stages = 0;
-  if (n <= 1) {  // nothing to swap
+  if (n <= 1) {  // nothing to swap: a plain upload, no stage
+    ctx->n_stages = 0;
     LB_TRY(lb_index_list_put(ctx, list, n, active));
     if (n && out_shuffling) out_shuffling[0] = active[0];
     return LB_OK;
   }
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  lb_ctx::IndexList& L = ctx->lists[list];
-  LB_TRY(list_reserve(ctx, L, n));
-  for (hipEvent_t& e : ctx->list_ev)
-    if (!e) LB_HIP(hipEventCreate(&e));
   const uint32_t n_digests = LB_SHUFFLE_ROUNDS * ((n + 255) / 256);
   HelperCall c(ctx);
   auto d_active = c.in(active, n);
@@ -2578,23 +2616,17 @@ int lb_index_list_shuffle(lb_ctx* ctx, uint32_t list, uint32_t n, const uint32_t
   auto d_pivots = c.scratch<uint32_t>(LB_SHUFFLE_ROUNDS);
   auto d_table = c.scratch<uint32_t>((size_t)n_digests * 8);  // [round][ceil(n/256)] digests
   LB_TRY(c.begin());
-  const bool timed = ctx->ccfg.stage_events;
-  if (timed) LB_HIP(hipEventRecord(ctx->list_ev[0], ctx->stream));
+  lb_ctx::IndexList& L = ctx->lists[list];
+  LB_TRY(L.reserve(ctx, n, 0));  // (begin() has retired the calls in flight, which may read the list)
+  LB_TRY(c.stage("shuffle"));
   LB_LAUNCH(k_shuffle_sources, blocks_for(n_digests, LB_LISTS_TPB), LB_LISTS_TPB, n, d_seed, d_pivots, d_table);
   LB_LAUNCH(k_shuffle_apply, blocks_for(n, LB_LISTS_TPB), LB_LISTS_TPB, n, (const uint32_t*)d_pivots,
             (const uint8_t*)(uint32_t*)d_table, d_active, L.d);
-  if (timed) LB_HIP(hipEventRecord(ctx->list_ev[1], ctx->stream));
+  LB_TRY(c.stage_end());
   L.n = 0;  // (until the kernels are known to have run)
-  if (out_shuffling)
-    LB_HIP(hipMemcpyAsync(out_shuffling, L.d, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_shuffling) LB_TRY(L.download(ctx, 0, out_shuffling, n));
   LB_TRY(c.end());
   L.n = n;
-  if (timed) {
-    LB_HIP(hipEventElapsedTime(&ctx->stage_ms[0], ctx->list_ev[0], ctx->list_ev[1]));
-    ctx->stage_name[0] = "shuffle";
-    ctx->stage_ops[0] = 0;
-    ctx->n_stages = 1;
-  }
   return LB_OK;
 }
 
@@ -2609,8 +2641,7 @@ int lb_index_list_read(lb_ctx* ctx, uint32_t list, uint32_t first, uint32_t n, u
     return LB_ERR_INVALID_ARGUMENT;
   if (n == 0) return LB_OK;
   LB_HIP(hipSetDevice(ctx->device));
-  LB_HIP(hipMemcpyAsync(out, ctx->lists[list].d + first, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost,
-                        ctx->stream));
+  LB_TRY(ctx->lists[list].download(ctx, first, out, n));
   LB_HIP(hipStreamSynchronize(ctx->stream));
   return LB_OK;
 }
@@ -2632,7 +2663,7 @@ int lb_aggregate_pubkeys_list(lb_ctx* ctx, uint32_t list, uint32_t first, uint32
 // ---- device-resident balance table (EffectiveBalanceIncrements mirror) -----------------
 int lb_balance_table_put(lb_ctx* ctx, uint32_t first, uint32_t n, const uint8_t* increments) {
   if (!ctx || (n && !increments)) return LB_ERR_INVALID_ARGUMENT;
-  if (first > ctx->bal_n || (uint64_t)first + n > 0x7fffffffu) {
+  if (first > ctx->bal.n || (uint64_t)first + n > 0x7fffffffu) {
     ctx->err = "lb_balance_table_put: first beyond the table's size";
     return LB_ERR_INVALID_ARGUMENT;
   }
@@ -2640,38 +2671,24 @@ int lb_balance_table_put(lb_ctx* ctx, uint32_t first, uint32_t n, const uint8_t*
   LB_HIP(hipSetDevice(ctx->device));
   LB_TRY(helper_slot(ctx));  // (nothing in flight reads the table; the order of calls is kept all the same)
   const uint32_t need = first + n;
-  if (need > ctx->bal_cap) {
-    uint64_t cap = (uint64_t)ctx->bal_cap * 2;
-    if (cap < need) cap = need;
-    if (cap < 4096) cap = 4096;
-    uint8_t* d = nullptr;
-    if (hipMalloc(&d, cap) != hipSuccess) {
-      ctx->err = "hipMalloc balance table failed";
-      return LB_ERR_OUT_OF_MEMORY;
-    }
-    if (ctx->bal_n) LB_HIP(hipMemcpyAsync(d, ctx->d_bal, ctx->bal_n, hipMemcpyDeviceToDevice, ctx->stream));
-    LB_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_bal) LB_HIP(hipFree(ctx->d_bal));
-    ctx->d_bal = d;
-    ctx->bal_cap = (uint32_t)cap;
-  }
-  LB_HIP(hipMemcpyAsync(ctx->d_bal + first, increments, n, hipMemcpyHostToDevice, ctx->stream));
+  LB_TRY(ctx->bal.reserve(ctx, need, ctx->bal.n));
+  LB_TRY(ctx->bal.upload(ctx, first, increments, n));
   LB_HIP(hipStreamSynchronize(ctx->stream));
-  if (need > ctx->bal_n) ctx->bal_n = need;
+  if (need > ctx->bal.n) ctx->bal.n = need;
   return LB_OK;
 }
 
 int lb_balance_table_size(const lb_ctx* ctx, uint32_t* out_n) {
   if (!ctx || !out_n) return LB_ERR_INVALID_ARGUMENT;
-  *out_n = ctx->bal_n;
+  *out_n = ctx->bal.n;
   return LB_OK;
 }
 
 int lb_balance_table_read(lb_ctx* ctx, uint32_t first, uint32_t n, uint8_t* out) {
-  if (!ctx || (n && !out) || (uint64_t)first + n > ctx->bal_n) return LB_ERR_INVALID_ARGUMENT;
+  if (!ctx || (n && !out) || (uint64_t)first + n > ctx->bal.n) return LB_ERR_INVALID_ARGUMENT;
   if (n == 0) return LB_OK;
   LB_HIP(hipSetDevice(ctx->device));
-  LB_HIP(hipMemcpyAsync(out, ctx->d_bal + first, n, hipMemcpyDeviceToHost, ctx->stream));
+  LB_TRY(ctx->bal.download(ctx, first, out, n));
   LB_HIP(hipStreamSynchronize(ctx->stream));
   return LB_OK;
 }
@@ -2715,10 +2732,6 @@ int lb_sample_by_balance(lb_ctx* ctx, uint32_t n_seeds, const uint8_t* seeds32, 
     ctx->err = std::string("lb_sample_by_balance: ") + why;
     return LB_ERR_INVALID_ARGUMENT;
   }
-  ctx->n_stages = 0;
-  LB_HIP(hipSetDevice(ctx->device));
-  for (hipEvent_t& e : ctx->list_ev)
-    if (!e) LB_HIP(hipEventCreate(&e));
   // the largest pass this call can come to, which is its last: the scratch is carved once
   // (the first pass is at most 4,096 and the bound at least 16,384, so no pass is smaller than the one before)
   uint32_t pass = LB_SAMPLE_FIRST_PASS(count), pass_max = pass;
@@ -2728,15 +2741,14 @@ int lb_sample_by_balance(lb_ctx* ctx, uint32_t n_seeds, const uint8_t* seeds32, 
   auto d_seeds = c.in(seeds32, (size_t)n_seeds * 32);
   auto d_pivots = c.scratch<uint32_t>((size_t)n_seeds * LB_SHUFFLE_ROUNDS);
   auto d_state = c.scratch<uint32_t>(1 + 2 * (size_t)n_seeds);  // max index; found[]; tried[]
-  auto d_out = c.scratch<uint32_t>((size_t)n_seeds * count);
+  auto d_out = c.out(out_indices, (size_t)n_seeds * count);
   auto d_cand = c.scratch<uint32_t>((size_t)n_seeds * pass_max);
   auto d_acc = c.scratch<uint8_t>((size_t)n_seeds * pass_max);
   LB_TRY(c.begin());
   uint32_t* const d_max = d_state;
   uint32_t* const d_found = d_max + 1;
   uint32_t* const d_tried = d_found + n_seeds;
-  const bool timed = ctx->ccfg.stage_events;
-  if (timed) LB_HIP(hipEventRecord(ctx->list_ev[0], ctx->stream));
+  LB_TRY(c.stage("sample"));
   LB_HIP(hipMemsetAsync(d_state, 0, sizeof(uint32_t) * (1 + 2 * (size_t)n_seeds), ctx->stream));
   LB_HIP(hipMemsetAsync(d_out, 0xff, sizeof(uint32_t) * (size_t)n_seeds * count, ctx->stream));  // LB_SAMPLE_NONE
   const uint32_t range_blocks = blocks_for(n, LB_LISTS_TPB);
@@ -2748,13 +2760,13 @@ int lb_sample_by_balance(lb_ctx* ctx, uint32_t n_seeds, const uint8_t* seeds32, 
   for (uint32_t base = 0; base < max_candidates; base += pass, pass = sample_next_pass(pass, n_seeds)) {
     LB_ENQUEUE(ctx->stream, k_sample_candidates, dim3(blocks_for(pass, LB_LISTS_TPB), n_seeds), LB_LISTS_TPB, n, count,
                base, pass, max_candidates, max_inc, d_seeds, (const uint32_t*)d_pivots, d_active,
-               (const uint8_t*)ctx->d_bal, ctx->bal_n, (const uint32_t*)d_found, d_cand, d_acc);
+               (const uint8_t*)ctx->bal.d, ctx->bal.n, (const uint32_t*)d_found, d_cand, d_acc);
     LB_LAUNCH(k_sample_select, n_seeds, LB_LISTS_TPB, count, base, pass, (const uint32_t*)d_cand,
               (const uint8_t*)d_acc, d_out, d_found, d_tried);
     LB_HIP(hipMemcpyAsync(state, d_state, sizeof(uint32_t) * (1 + (size_t)n_seeds), hipMemcpyDeviceToHost,
                           ctx->stream));
     LB_HIP(hipStreamSynchronize(ctx->stream));
-    if (state[0] >= ctx->bal_n) {  // (the candidates kernel read no increment outside the table)
+    if (state[0] >= ctx->bal.n) {  // (the candidates kernel read no increment outside the table)
       ctx->err = "lb_sample_by_balance: an active index at or beyond the balance table's size";
       return LB_ERR_INVALID_ARGUMENT;
     }
@@ -2762,29 +2774,21 @@ int lb_sample_by_balance(lb_ctx* ctx, uint32_t n_seeds, const uint8_t* seeds32, 
     for (uint32_t s = 0; s < n_seeds; s++) filled = filled && found[s] >= count;
     if (filled) break;
   }
-  if (timed) LB_HIP(hipEventRecord(ctx->list_ev[1], ctx->stream));
+  LB_TRY(c.stage_end());
   if (store_list != LB_NO_LIST && found[0] == count) {  // device to device; an unfilled seed leaves the list
     lb_ctx::IndexList& L = ctx->lists[store_list];
-    LB_TRY(list_reserve(ctx, L, count));
+    LB_TRY(L.reserve(ctx, count, 0));
     L.n = 0;  // (until the copy is known to have run)
     LB_HIP(hipMemcpyAsync(L.d, d_out, sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToDevice, ctx->stream));
     LB_HIP(hipStreamSynchronize(ctx->stream));
     L.n = count;
   }
-  LB_HIP(hipMemcpyAsync(out_indices, d_out, sizeof(uint32_t) * (size_t)n_seeds * count, hipMemcpyDeviceToHost,
-                        ctx->stream));
   LB_HIP(hipMemcpyAsync(state + 1 + n_seeds, d_tried, sizeof(uint32_t) * (size_t)n_seeds, hipMemcpyDeviceToHost,
                         ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
+  LB_TRY(c.end());
   for (uint32_t s = 0; s < n_seeds; s++) {
     if (out_found) out_found[s] = found[s];
     if (out_tried) out_tried[s] = found[s] == count ? state[1 + n_seeds + s] : max_candidates;
-  }
-  if (timed) {
-    LB_HIP(hipEventElapsedTime(&ctx->stage_ms[0], ctx->list_ev[0], ctx->list_ev[1]));
-    ctx->stage_name[0] = "sample";
-    ctx->stage_ops[0] = 0;
-    ctx->n_stages = 1;
   }
   return LB_OK;
 }
@@ -3019,8 +3023,8 @@ int sm_front(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint32_t mod
   uint8_t* d_jbad = sm_d<uint8_t>(sl, L.d_jbad);
   LB_TRY(begin_call(ctx, sl));
   LB_HIP(hipMemcpyAsync(sl.d_ws, sl.h_pin, L.in_bytes, hipMemcpyHostToDevice, sl.st[0]));
-  const PkSource src_pk{by_index ? d_rows : d_pks, by_index ? (const uint32_t*)d_pks : nullptr, ctx->d_table,
-                        ctx->table_n};
+  const PkSource src_pk{by_index ? d_rows : d_pks, by_index ? (const uint32_t*)d_pks : nullptr, ctx->table.d,
+                        ctx->table.n};
   const uint32_t agg_grid = nj < 16384u ? nj : 16384u;
   // randomized sums: the G1 side needs only the upload, so with a second stream it runs there,
   // beside the decode and the G2 side (joined below, before the aggregated sets are read)
@@ -3040,7 +3044,7 @@ int sm_front(lb_ctx* ctx, Slot& sl, const lb_same_message_batch* b, uint32_t mod
     uint8_t* d_dec_pre = sm_d<uint8_t>(sl, L.dec_pre);
     LB_STAGE("sm_decode", 0, k_sm_dec_prep, blocks_for(ns, 256), 256u, ns, d_sigs, d_sigo, d_dec_in, d_dec_fl,
              d_dec_pre);
-    LB_STAGE("sm_decode", 0, k_lp_dec, ns, LB_LP_DEC_ROWS * 16u, ctx->d_lp + LB_LP_PROGS[LB_LP_PROG_SIG_DECODE].off, ns,
+    LB_STAGE("sm_decode", 0, k_lp_dec, ns, LB_LP_DEC_ROWS * 16u, ctx->d_lp.d + LB_LP_PROGS[LB_LP_PROG_SIG_DECODE].off, ns,
              (const uint32_t*)d_dec_in, (const uint32_t*)d_dec_fl, d_dec_out, d_dec_ofl);
     LB_STAGE("sm_decode", 0, k_sm_dec_finish, blocks_for(ns, 256), 256u, ns, (const uint8_t*)d_dec_pre,
              (const uint32_t*)d_dec_in, (const uint32_t*)d_dec_fl, (const uint32_t*)d_dec_out,
@@ -3611,7 +3615,7 @@ int lb_lp_program_run(lb_ctx* ctx, uint32_t prog, const uint32_t* prog_words, si
   auto d_st = c.scratch<unsigned long long>((size_t)(n_rounds + 1) * LB_LP_STAMPS, stamps != nullptr);
   LB_TRY(c.begin());
   if (!prog_words) LB_TRY(lp_ensure(ctx));
-  const uint32_t* d_prog = prog_words ? (const uint32_t*)d_words : ctx->d_lp + LB_LP_PROGS[prog].off;
+  const uint32_t* d_prog = prog_words ? (const uint32_t*)d_words : ctx->d_lp.d + LB_LP_PROGS[prog].off;
   if (n_inflag) LB_HIP(hipMemcpyAsync(d_fl, in_flags, (fl_w - 1) * 4, hipMemcpyHostToDevice, ctx->stream));
   ScopedEvent e0, e1;
   LB_HIP(hipEventCreate(&e0.e));
@@ -3670,72 +3674,43 @@ int lb_sign(lb_ctx* ctx, uint32_t n, const uint8_t* sk32, const uint8_t* message
 // ============================================================================
 namespace {
 
-// device buffers of one KZG call, carved from the KZG workspace
+// What persists across the KZG calls, on first use: the setup's pair of slots and the roots
+// table.  After the call's begin(), which has retired the calls in flight.
+int kzg_ensure(lb_ctx* ctx) {
+  KzgState& k = ctx->kzg;
+  LB_TRY(k.neg_tau.reserve(ctx, 2, 0));
+  if (k.roots.n) return LB_OK;
+  LB_TRY(k.roots.reserve(ctx, LB_KZG_N, 0));
+  LB_LAUNCH(k_kzg_roots, LB_KZG_N / 256, 256, k.roots.d);
+  LB_HIP(hipStreamSynchronize(ctx->stream));
+  k.roots.n = LB_KZG_N;  // (built)
+  return LB_OK;
+}
+
+// device buffers of a verify call's pairing tail, as the call declared them
 struct KzgBufs {
-  uint8_t *blobs, *com, *proofs, *z, *y, *status, *pt_status, *skip, *scalars, *verdict;
-  g1j *P, *lad, *AB;
-  fp12* f;
+  CarvePtr<const uint8_t> com, proofs, z, y;
+  CarvePtr<uint8_t> status, pt_status, skip, scalars, verdict;
+  CarvePtr<g1j> P, lad, AB;
+  CarvePtr<fp12> f;
 };
 
-// The roots table, the workspace and the timing events, on first use; waits for calls in flight.
-int kzg_ensure(lb_ctx* ctx, KzgBufs& b) {
-  LB_HIP(hipSetDevice(ctx->device));
-  LB_TRY(helper_slot(ctx));
-  KzgState& k = ctx->kzg;
-  // the buffers of a call of LB_KZG_MAX_BLOBS blobs: the workspace is this list's total
-  constexpr size_t M = LB_KZG_MAX_BLOBS;
-  Carve<14> c;
-  auto blobs = c.scratch<uint8_t>(M * LB_KZG_BLOB_BYTES);
-  auto com = c.scratch<uint8_t>(M * 48);
-  auto proofs = c.scratch<uint8_t>(M * 48);
-  auto z = c.scratch<uint8_t>(M * 32);
-  auto y = c.scratch<uint8_t>(M * 32);
-  auto status = c.scratch<uint8_t>(M);
-  auto pt_status = c.scratch<uint8_t>(2 * M);
-  auto skip = c.scratch<uint8_t>(16);
-  auto scalars = c.scratch<uint8_t>((3 * M + 1) * 32);
-  auto verdict = c.scratch<uint8_t>(M);
-  auto P = c.scratch<g1j>(2 * M + 1);
-  auto lad = c.scratch<g1j>(3 * M + 1);
-  auto AB = c.scratch<g1j>(2 * M);
-  auto f = c.scratch<fp12>(2 * M);
-  const size_t bytes = c.layout();
-  if (!k.d_ws) {
-    if (hipMalloc(&k.d_ws, bytes) != hipSuccess) {
-      k.d_ws = nullptr;
-      ctx->err = "hipMalloc KZG workspace failed";
-      return LB_ERR_OUT_OF_MEMORY;
-    }
-    k.ws_cap = bytes;
-  }
-  if (!c.fits(k.ws_cap)) {
-    ctx->err = "KZG workspace overflow";
-    return LB_ERR_OUT_OF_MEMORY;
-  }
-  c.bind(k.d_ws);
-  b = KzgBufs{blobs, com, proofs, z, y, status, pt_status, skip, scalars, verdict, P, lad, AB, f};
-  if (!k.d_neg_tau && hipMalloc(&k.d_neg_tau, 2 * sizeof(g2a)) != hipSuccess) {
-    k.d_neg_tau = nullptr;
-    ctx->err = "hipMalloc KZG setup failed";
-    return LB_ERR_OUT_OF_MEMORY;
-  }
-  for (hipEvent_t& e : k.ev)
-    if (!e) LB_HIP(hipEventCreate(&e));
-  if (!k.d_roots) {
-    fr* d = nullptr;
-    if (hipMalloc(&d, sizeof(fr) * LB_KZG_N) != hipSuccess) {
-      ctx->err = "hipMalloc KZG roots failed";
-      return LB_ERR_OUT_OF_MEMORY;
-    }
-    hipLaunchKernelGGL(k_kzg_roots, dim3(LB_KZG_N / 256), dim3(256), 0, ctx->stream, d);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-      (void)hipFree(d);
-      ctx->err = "k_kzg_roots failed";
-      return LB_ERR_DEVICE;
-    }
-    k.d_roots = d;
-  }
-  return LB_OK;
+// The tail's own buffers for n items, behind the commitments, proofs, z, y and statuses the
+// call has declared; `verdicts` (n bytes) is where end() leaves them
+KzgBufs kzg_declare_tail(HelperCall& c, uint32_t n, CarvePtr<const uint8_t> com, CarvePtr<const uint8_t> proofs,
+                         CarvePtr<const uint8_t> z, CarvePtr<const uint8_t> y, CarvePtr<uint8_t> status,
+                         uint8_t* verdicts) {
+  const size_t m = n;
+  KzgBufs b{com, proofs, z, y, status};
+  b.pt_status = c.scratch<uint8_t>(2 * m);
+  b.skip = c.scratch<uint8_t>(16);
+  b.scalars = c.scratch<uint8_t>((3 * m + 1) * 32);
+  b.verdict = c.out(verdicts, m);
+  b.P = c.scratch<g1j>(2 * m + 1);
+  b.lad = c.scratch<g1j>(3 * m + 1);
+  b.AB = c.scratch<g1j>(2 * m);
+  b.f = c.scratch<fp12>(2 * m);
+  return b;
 }
 
 // The pairing tail on device-resident commitments, proofs, z and y: decode, statuses and
@@ -3761,48 +3736,36 @@ int kzg_tail(lb_ctx* ctx, const KzgBufs& b, uint32_t n, uint32_t mode) {
     m = n;
     LB_LAUNCH(k_kzg_each_sum, blocks_for(n), TPB, n, (const g1j*)b.P, (const g1j*)b.lad, b.AB);
   }
-  LB_LAUNCH(k_kzg_miller, blocks_for(2 * m), TPB, m, (const g1j*)b.AB, (const g2a*)k.d_neg_tau,
+  LB_LAUNCH(k_kzg_miller, blocks_for(2 * m), TPB, m, (const g1j*)b.AB, (const g2a*)k.neg_tau.d,
             mode == LB_KZG_BATCH ? (const uint8_t*)b.skip : (const uint8_t*)nullptr, b.f);
   LB_LAUNCH(k_kzg_final, blocks_for(m), TPB, m, mode, (const fp12*)b.f, (const uint8_t*)b.status,
             (const uint8_t*)b.skip, b.verdict);
   return LB_OK;
 }
 
-// stage times of a KZG call: names[i] spans ev[first + i] .. ev[first + i + 1]
-int kzg_publish_times(lb_ctx* ctx, int first, int count, const char* const* names) {
-  ctx->n_stages = 0;
-  if (!ctx->ccfg.stage_events) return LB_OK;
-  for (int i = 0; i < count; i++) {
-    float ms = 0.f;
-    LB_HIP(hipEventElapsedTime(&ms, ctx->kzg.ev[first + i], ctx->kzg.ev[first + i + 1]));
-    ctx->stage_ms[i] = ms;
-    ctx->stage_name[i] = names[i];
-    ctx->stage_ops[i] = 0;
-  }
-  ctx->n_stages = count;
-  return LB_OK;
-}
-
-// verdicts of a verify call once its tail is enqueued: statuses, the batch verdict and,
-// for a failed batch with out_each, every item's own check
-int kzg_finish_verify(lb_ctx* ctx, const KzgBufs& b, uint32_t n, int32_t* out_ok, uint8_t* out_status,
-                      uint8_t* out_each) {
+// What a verify call's two outputs come back into (kzg_declare_tail, kzg_finish_verify)
+struct KzgVerdicts {
   uint8_t st[LB_KZG_MAX_BLOBS], v[LB_KZG_MAX_BLOBS];
-  LB_HIP(hipMemcpyAsync(st, b.status, n, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipMemcpyAsync(v, b.verdict, 1, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  bool ok = v[0] == 1;
-  for (uint32_t i = 0; i < n; i++) ok = ok && st[i] == LB_KZG_OK;
+};
+
+// verdicts of a verify call once its tail is enqueued: statuses, the batch verdict ([0] of the
+// verdicts a batch pass leaves) and, for a failed batch with out_each, every item's own check:
+// the per-item tail on the buffers still bound, and end() once more for its verdicts
+int kzg_finish_verify(HelperCall& c, const KzgBufs& b, KzgVerdicts& r, uint32_t n, int32_t* out_ok,
+                      uint8_t* out_status, uint8_t* out_each) {
+  lb_ctx* ctx = c.ctx;
+  LB_TRY(c.end());
+  bool ok = r.v[0] == 1;
+  for (uint32_t i = 0; i < n; i++) ok = ok && r.st[i] == LB_KZG_OK;
   *out_ok = ok ? 1 : 0;
-  if (out_status) memcpy(out_status, st, n);
+  if (out_status) memcpy(out_status, r.st, n);
   if (out_each) {
     if (ok) {
       memset(out_each, 1, n);
     } else {
       LB_TRY(kzg_tail(ctx, b, n, LB_KZG_EACH));
-      LB_HIP(hipMemcpyAsync(v, b.verdict, n, hipMemcpyDeviceToHost, ctx->stream));
-      LB_HIP(hipStreamSynchronize(ctx->stream));
-      for (uint32_t i = 0; i < n; i++) out_each[i] = (st[i] == LB_KZG_OK && v[i] == 1) ? 1 : 0;
+      LB_TRY(c.end());
+      for (uint32_t i = 0; i < n; i++) out_each[i] = (r.st[i] == LB_KZG_OK && r.v[i] == 1) ? 1 : 0;
     }
   }
   return LB_OK;
@@ -3820,8 +3783,6 @@ int kzg_check_verify_args(lb_ctx* ctx, uint32_t n, bool ptrs_ok, const char* wha
   return LB_OK;
 }
 
-#define LB_KZG_UP(dst, src, bytes) LB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream))
-
 }  // namespace
 
 extern "C" {
@@ -3837,15 +3798,16 @@ int lb_kzg_load_setup(lb_ctx* ctx, const uint8_t* g2_tau96) {
     ctx->err = "lb_kzg_load_setup: null pointer";
     return LB_ERR_INVALID_ARGUMENT;
   }
-  KzgBufs b;
-  LB_TRY(kzg_ensure(ctx, b));
+  uint8_t st = 0xff;
+  HelperCall c(ctx);
+  auto d_tau = c.in(g2_tau96, 96);
+  auto d_st = c.out(&st, 1);
+  LB_TRY(c.begin());
+  LB_TRY(kzg_ensure(ctx));
   KzgState& k = ctx->kzg;
   // the candidate is checked into slot [1] and copied over the loaded setup only when accepted
-  LB_KZG_UP(b.com, g2_tau96, 96);
-  LB_LAUNCH(k_kzg_setup_g2, 1u, TPB, (const uint8_t*)b.com, k.d_neg_tau + 1, b.status);
-  uint8_t st = 0xff;
-  LB_HIP(hipMemcpyAsync(&st, b.status, 1, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
+  LB_LAUNCH(k_kzg_setup_g2, 1u, TPB, d_tau, k.neg_tau.d + 1, d_st);
+  LB_TRY(c.end());
   if (st != LB_ST_OK) {
     ctx->err = std::string("lb_kzg_load_setup: KZG_SETUP_G2_MONOMIAL[1] ") +
                (st == LB_ST_PK_INFINITY ? "is the point at infinity"
@@ -3854,7 +3816,7 @@ int lb_kzg_load_setup(lb_ctx* ctx, const uint8_t* g2_tau96) {
                                            : "does not decode");
     return LB_ERR_INVALID_ARGUMENT;
   }
-  LB_HIP(hipMemcpyAsync(k.d_neg_tau, k.d_neg_tau + 1, sizeof(g2a), hipMemcpyDeviceToDevice, ctx->stream));
+  LB_HIP(hipMemcpyAsync(k.neg_tau.d, k.neg_tau.d + 1, sizeof(g2a), hipMemcpyDeviceToDevice, ctx->stream));
   LB_HIP(hipStreamSynchronize(ctx->stream));
   k.loaded = true;
   return LB_OK;
@@ -3866,22 +3828,19 @@ int lb_kzg_blob_challenges(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const 
   if (n == 0) return LB_OK;
   LB_TRY(kzg_check_verify_args(ctx, n, blobs && commitments48 && out_z32 && out_y32 && out_status,
                                "lb_kzg_blob_challenges"));
-  KzgBufs b;
-  LB_TRY(kzg_ensure(ctx, b));
-  LB_KZG_UP(b.blobs, blobs, (size_t)n * LB_KZG_BLOB_BYTES);
-  LB_KZG_UP(b.com, commitments48, (size_t)n * 48);
-  LB_HIP(hipEventRecord(ctx->kzg.ev[0], ctx->stream));
-  LB_LAUNCH(k_kzg_hash, n, LB_KZG_HASH_TPB, (const uint8_t*)b.blobs, (const uint8_t*)b.com, b.z, b.status);
-  LB_HIP(hipEventRecord(ctx->kzg.ev[1], ctx->stream));
-  LB_LAUNCH(k_kzg_eval, n, LB_KZG_EVAL_TPB, (const uint8_t*)b.blobs, (const fr*)ctx->kzg.d_roots,
-            (const uint8_t*)b.z, b.y, b.status);
-  LB_HIP(hipEventRecord(ctx->kzg.ev[2], ctx->stream));
-  LB_HIP(hipMemcpyAsync(out_z32, b.z, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipMemcpyAsync(out_y32, b.y, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipMemcpyAsync(out_status, b.status, n, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  static const char* const names[] = {"kzg_hash", "kzg_eval"};
-  return kzg_publish_times(ctx, 0, 2, names);
+  HelperCall c(ctx);
+  auto d_blobs = c.in(blobs, (size_t)n * LB_KZG_BLOB_BYTES);
+  auto d_com = c.in(commitments48, (size_t)n * 48);
+  auto d_z = c.out(out_z32, (size_t)n * 32);
+  auto d_y = c.out(out_y32, (size_t)n * 32);
+  auto d_st = c.out(out_status, n);
+  LB_TRY(c.begin());
+  LB_TRY(kzg_ensure(ctx));
+  LB_TRY(c.stage("kzg_hash"));
+  LB_LAUNCH(k_kzg_hash, n, LB_KZG_HASH_TPB, d_blobs, d_com, d_z, d_st);
+  LB_TRY(c.stage("kzg_eval"));
+  LB_LAUNCH(k_kzg_eval, n, LB_KZG_EVAL_TPB, d_blobs, (const fr*)ctx->kzg.roots.d, (const uint8_t*)d_z, d_y, d_st);
+  return c.end();
 }
 
 int lb_kzg_evaluate(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* z32, uint8_t* out_y32,
@@ -3889,20 +3848,17 @@ int lb_kzg_evaluate(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t
   if (!ctx) return LB_ERR_INVALID_ARGUMENT;
   if (n == 0) return LB_OK;
   LB_TRY(kzg_check_verify_args(ctx, n, blobs && z32 && out_y32 && out_status, "lb_kzg_evaluate"));
-  KzgBufs b;
-  LB_TRY(kzg_ensure(ctx, b));
-  LB_KZG_UP(b.blobs, blobs, (size_t)n * LB_KZG_BLOB_BYTES);
-  LB_KZG_UP(b.z, z32, (size_t)n * 32);
-  LB_HIP(hipMemsetAsync(b.status, 0, n, ctx->stream));
-  LB_HIP(hipEventRecord(ctx->kzg.ev[1], ctx->stream));
-  LB_LAUNCH(k_kzg_eval, n, LB_KZG_EVAL_TPB, (const uint8_t*)b.blobs, (const fr*)ctx->kzg.d_roots,
-            (const uint8_t*)b.z, b.y, b.status);
-  LB_HIP(hipEventRecord(ctx->kzg.ev[2], ctx->stream));
-  LB_HIP(hipMemcpyAsync(out_y32, b.y, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipMemcpyAsync(out_status, b.status, n, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  static const char* const names[] = {"kzg_eval"};
-  return kzg_publish_times(ctx, 1, 1, names);
+  HelperCall c(ctx);
+  auto d_blobs = c.in(blobs, (size_t)n * LB_KZG_BLOB_BYTES);
+  auto d_z = c.in(z32, (size_t)n * 32);
+  auto d_y = c.out(out_y32, (size_t)n * 32);
+  auto d_st = c.out(out_status, n);
+  LB_TRY(c.begin());
+  LB_TRY(kzg_ensure(ctx));
+  LB_HIP(hipMemsetAsync(d_st, 0, n, ctx->stream));
+  LB_TRY(c.stage("kzg_eval"));
+  LB_LAUNCH(k_kzg_eval, n, LB_KZG_EVAL_TPB, d_blobs, (const fr*)ctx->kzg.roots.d, d_z, d_y, d_st);
+  return c.end();
 }
 
 int lb_kzg_verify_blob_proof_batch(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* commitments48,
@@ -3919,22 +3875,24 @@ int lb_kzg_verify_blob_proof_batch(lb_ctx* ctx, uint32_t n, const uint8_t* blobs
     *out_ok = 1;
     return LB_OK;
   }
-  KzgBufs b;
-  LB_TRY(kzg_ensure(ctx, b));
-  LB_KZG_UP(b.blobs, blobs, (size_t)n * LB_KZG_BLOB_BYTES);
-  LB_KZG_UP(b.com, commitments48, (size_t)n * 48);
-  LB_KZG_UP(b.proofs, proofs48, (size_t)n * 48);
-  LB_HIP(hipEventRecord(ctx->kzg.ev[0], ctx->stream));
-  LB_LAUNCH(k_kzg_hash, n, LB_KZG_HASH_TPB, (const uint8_t*)b.blobs, (const uint8_t*)b.com, b.z, b.status);
-  LB_HIP(hipEventRecord(ctx->kzg.ev[1], ctx->stream));
-  LB_LAUNCH(k_kzg_eval, n, LB_KZG_EVAL_TPB, (const uint8_t*)b.blobs, (const fr*)ctx->kzg.d_roots,
-            (const uint8_t*)b.z, b.y, b.status);
-  LB_HIP(hipEventRecord(ctx->kzg.ev[2], ctx->stream));
+  KzgVerdicts r;
+  HelperCall c(ctx);
+  auto d_blobs = c.in(blobs, (size_t)n * LB_KZG_BLOB_BYTES);
+  auto d_com = c.in(commitments48, (size_t)n * 48);
+  auto d_proofs = c.in(proofs48, (size_t)n * 48);
+  auto d_z = c.scratch<uint8_t>((size_t)n * 32);
+  auto d_y = c.scratch<uint8_t>((size_t)n * 32);
+  auto d_st = c.out(r.st, n);
+  const KzgBufs b = kzg_declare_tail(c, n, d_com, d_proofs, {d_z.off, d_z.base}, {d_y.off, d_y.base}, d_st, r.v);
+  LB_TRY(c.begin());
+  LB_TRY(kzg_ensure(ctx));
+  LB_TRY(c.stage("kzg_hash"));
+  LB_LAUNCH(k_kzg_hash, n, LB_KZG_HASH_TPB, d_blobs, d_com, d_z, d_st);
+  LB_TRY(c.stage("kzg_eval"));
+  LB_LAUNCH(k_kzg_eval, n, LB_KZG_EVAL_TPB, d_blobs, (const fr*)ctx->kzg.roots.d, (const uint8_t*)d_z, d_y, d_st);
+  LB_TRY(c.stage("kzg_tail"));
   LB_TRY(kzg_tail(ctx, b, n, LB_KZG_BATCH));
-  LB_HIP(hipEventRecord(ctx->kzg.ev[3], ctx->stream));
-  LB_TRY(kzg_finish_verify(ctx, b, n, out_ok, out_status, out_each));
-  static const char* const names[] = {"kzg_hash", "kzg_eval", "kzg_tail"};
-  return kzg_publish_times(ctx, 0, 3, names);
+  return kzg_finish_verify(c, b, r, n, out_ok, out_status, out_each);
 }
 
 int lb_kzg_verify_proof_batch(lb_ctx* ctx, uint32_t n, const uint8_t* commitments48, const uint8_t* z32,
@@ -3951,19 +3909,20 @@ int lb_kzg_verify_proof_batch(lb_ctx* ctx, uint32_t n, const uint8_t* commitment
     *out_ok = 1;
     return LB_OK;
   }
-  KzgBufs b;
-  LB_TRY(kzg_ensure(ctx, b));
-  LB_KZG_UP(b.com, commitments48, (size_t)n * 48);
-  LB_KZG_UP(b.proofs, proofs48, (size_t)n * 48);
-  LB_KZG_UP(b.z, z32, (size_t)n * 32);
-  LB_KZG_UP(b.y, y32, (size_t)n * 32);
-  LB_HIP(hipMemsetAsync(b.status, 0, n, ctx->stream));
-  LB_HIP(hipEventRecord(ctx->kzg.ev[2], ctx->stream));
+  KzgVerdicts r;
+  HelperCall c(ctx);
+  auto d_com = c.in(commitments48, (size_t)n * 48);
+  auto d_proofs = c.in(proofs48, (size_t)n * 48);
+  auto d_z = c.in(z32, (size_t)n * 32);
+  auto d_y = c.in(y32, (size_t)n * 32);
+  auto d_st = c.out(r.st, n);
+  const KzgBufs b = kzg_declare_tail(c, n, d_com, d_proofs, d_z, d_y, d_st, r.v);
+  LB_TRY(c.begin());
+  LB_TRY(kzg_ensure(ctx));
+  LB_HIP(hipMemsetAsync(d_st, 0, n, ctx->stream));
+  LB_TRY(c.stage("kzg_tail"));
   LB_TRY(kzg_tail(ctx, b, n, LB_KZG_BATCH));
-  LB_HIP(hipEventRecord(ctx->kzg.ev[3], ctx->stream));
-  LB_TRY(kzg_finish_verify(ctx, b, n, out_ok, out_status, out_each));
-  static const char* const names[] = {"kzg_tail"};
-  return kzg_publish_times(ctx, 2, 1, names);
+  return kzg_finish_verify(c, b, r, n, out_ok, out_status, out_each);
 }
 
 }  // extern "C"
@@ -3973,72 +3932,35 @@ int lb_kzg_verify_proof_batch(lb_ctx* ctx, uint32_t n, const uint8_t* commitment
 // ============================================================================
 namespace {
 
-// device buffers of the fixed-base MSM (a group of LB_KZG_MSM_GROUP jobs) and of a G1 setup
-// load, carved from the MSM workspace; the two lists share it (a load and a call never overlap)
+// device buffers of the fixed-base MSM: one group of jobs at a time
 struct KzgMsmBufs {
-  uint8_t *quot, *out48;
-  uint32_t *keys, *sorted, *hist, *off, *coff, *cursor;
-  g1j *csum, *bsum, *G;
-  // setup load
-  uint8_t *in48, *pt_status;
-  g1j* J;
+  CarvePtr<uint32_t> keys, sorted, hist, off, coff, cursor;
+  CarvePtr<g1j> csum, bsum, G;
 };
 
 static_assert(sizeof(g1j) == SZ_G1J, "carve record size");
 
-// The window tables (two: the loaded one and a candidate's) and the MSM workspace, on first use
-int kzg_msm_ensure(lb_ctx* ctx, KzgMsmBufs& m) {
-  KzgState& k = ctx->kzg;
-  constexpr size_t M = LB_KZG_MAX_BLOBS, G = LB_KZG_MSM_GROUP, NB = LB_KZG_MSM_NB;
-  // a call: the quotients and results of all its items, then one group's MSM
-  Carve<11> c;
-  auto quot = c.scratch<uint8_t>(M * LB_KZG_BLOB_BYTES);
-  auto out48 = c.scratch<uint8_t>(M * 48);
-  auto keys = c.scratch<uint32_t>(G * LB_KZG_MSM_ENT);
-  auto sorted = c.scratch<uint32_t>(G * LB_KZG_MSM_ENT);
-  auto hist = c.scratch<uint32_t>(G * NB);
-  auto off = c.scratch<uint32_t>(G * (NB + 1));
-  auto coff = c.scratch<uint32_t>(G * (NB + 1));
-  auto cursor = c.scratch<uint32_t>(G * NB);
-  auto csum = c.scratch<g1j>(G * LB_KZG_MSM_MAXC);
-  auto bsum = c.scratch<g1j>(G * NB);
-  auto Gk = c.scratch<g1j>(G * 8);
-  // a setup load: the file's points, their statuses, the Jacobian multiples before the inversion
-  Carve<3> s;
-  auto in48 = s.scratch<uint8_t>((size_t)LB_KZG_N * 48);
-  auto pt_status = s.scratch<uint8_t>(LB_KZG_N);
-  auto J = s.scratch<g1j>(LB_KZG_MSM_ENT);
-  const size_t call_bytes = c.layout(), load_bytes = s.layout();
-  const size_t bytes = call_bytes > load_bytes ? call_bytes : load_bytes;
-  if (!k.d_msm_ws) {
-    if (hipMalloc(&k.d_msm_ws, bytes) != hipSuccess) {
-      k.d_msm_ws = nullptr;
-      ctx->err = "hipMalloc KZG MSM workspace failed";
-      return LB_ERR_OUT_OF_MEMORY;
-    }
-    k.msm_cap = bytes;
-  }
-  if (!c.fits(k.msm_cap) || !s.fits(k.msm_cap)) {
-    ctx->err = "KZG MSM workspace overflow";
-    return LB_ERR_OUT_OF_MEMORY;
-  }
-  c.bind(k.d_msm_ws);
-  s.bind(k.d_msm_ws);
-  m = KzgMsmBufs{quot, out48, keys, sorted, hist, off, coff, cursor, csum, bsum, Gk, in48, pt_status, J};
-  for (g1a*& t : k.d_g1_tab)
-    if (!t && hipMalloc(&t, sizeof(g1a) * LB_KZG_MSM_ENT) != hipSuccess) {
-      t = nullptr;
-      ctx->err = "hipMalloc KZG G1 table failed";
-      return LB_ERR_OUT_OF_MEMORY;
-    }
-  return LB_OK;
+// The MSM's buffers for a call of n jobs: those of one group, the call's largest (kzg_msm)
+KzgMsmBufs kzg_declare_msm(HelperCall& c, uint32_t n) {
+  const size_t g = n < LB_KZG_MSM_GROUP ? n : LB_KZG_MSM_GROUP, NB = LB_KZG_MSM_NB;
+  KzgMsmBufs m;
+  m.keys = c.scratch<uint32_t>(g * LB_KZG_MSM_ENT);
+  m.sorted = c.scratch<uint32_t>(g * LB_KZG_MSM_ENT);
+  m.hist = c.scratch<uint32_t>(g * NB);
+  m.off = c.scratch<uint32_t>(g * (NB + 1));
+  m.coff = c.scratch<uint32_t>(g * (NB + 1));
+  m.cursor = c.scratch<uint32_t>(g * NB);
+  m.csum = c.scratch<g1j>(g * LB_KZG_MSM_MAXC);
+  m.bsum = c.scratch<g1j>(g * NB);
+  m.G = c.scratch<g1j>(g * 8);
+  return m;
 }
 
 // out48[k] = sum_i scalars[k][i] L[i] for n device-resident jobs, in groups of LB_KZG_MSM_GROUP;
 // a scalar >= r sets status[k] = bad_code (kept when set already); such a job's output is zero
 int kzg_msm(lb_ctx* ctx, const KzgMsmBufs& m, uint32_t n, const uint8_t* scalars, uint8_t* status, uint8_t bad_code,
             uint8_t* out48) {
-  const g1a* T = ctx->kzg.d_g1_tab[ctx->kzg.g1_cur];
+  const g1a* T = ctx->kzg.g1_tab[ctx->kzg.g1_cur].d;
   for (uint32_t j0 = 0; j0 < n; j0 += LB_KZG_MSM_GROUP) {
     const uint32_t g = n - j0 < LB_KZG_MSM_GROUP ? n - j0 : LB_KZG_MSM_GROUP;
     const uint8_t* sc = scalars + (size_t)j0 * LB_KZG_BLOB_BYTES;
@@ -4067,42 +3989,55 @@ int kzg_check_g1_args(lb_ctx* ctx, uint32_t n, bool ptrs_ok, const char* what) {
   return LB_OK;
 }
 
+// n jobs of 4096 scalars each up, their MSM, results and statuses down
+int kzg_lincomb(lb_ctx* ctx, uint32_t n, const uint8_t* scalars32, uint8_t bad_code, uint8_t* out48,
+                uint8_t* out_status) {
+  HelperCall c(ctx);
+  auto d_sc = c.in(scalars32, (size_t)n * LB_KZG_BLOB_BYTES);
+  auto d_st = c.out(out_status, n);
+  auto d_out = c.out(out48, (size_t)n * 48);
+  const KzgMsmBufs m = kzg_declare_msm(c, n);
+  LB_TRY(c.begin());
+  LB_TRY(kzg_ensure(ctx));
+  LB_HIP(hipMemsetAsync(d_st, 0, n, ctx->stream));
+  LB_TRY(c.stage("kzg_msm"));
+  LB_TRY(kzg_msm(ctx, m, n, d_sc, d_st, bad_code, d_out));
+  return c.end();
+}
+
 // blobs (and commitments or z) up; then the quotients' MSM.  with_hash: z from the transcript
 // (compute_blob_kzg_proof), else z is given (compute_kzg_proof).
 int kzg_prove(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* com48, const uint8_t* z32,
               uint8_t* out_proofs48, uint8_t* out_y32, uint8_t* out_status) {
-  KzgBufs b;
-  LB_TRY(kzg_ensure(ctx, b));
-  KzgMsmBufs m;
-  LB_TRY(kzg_msm_ensure(ctx, m));
-  KzgState& k = ctx->kzg;
-  LB_KZG_UP(b.blobs, blobs, (size_t)n * LB_KZG_BLOB_BYTES);
-  int first = 1;
+  HelperCall c(ctx);
+  auto d_blobs = c.in(blobs, (size_t)n * LB_KZG_BLOB_BYTES);
+  auto d_com = c.in(com48, (size_t)n * 48, com48 != nullptr);
+  // z: the caller's, or the transcript's; y: kept on the device when the caller does not want it
+  // (CARVE_OUT without a host pointer is scratch)
+  auto d_z = c.add<uint8_t>(com48 ? CARVE_SCRATCH : CARVE_IN, (size_t)n * 32, true, z32, nullptr);
+  auto d_y = c.out(out_y32, (size_t)n * 32);
+  auto d_st = c.out(out_status, n);
+  auto d_quot = c.scratch<uint8_t>((size_t)n * LB_KZG_BLOB_BYTES);
+  auto d_out = c.out(out_proofs48, (size_t)n * 48);
+  const KzgMsmBufs m = kzg_declare_msm(c, n);
+  LB_TRY(c.begin());
+  LB_TRY(kzg_ensure(ctx));
+  const fr* roots = ctx->kzg.roots.d;
   if (com48) {
-    first = 0;
-    LB_KZG_UP(b.com, com48, (size_t)n * 48);
-    LB_HIP(hipEventRecord(k.ev[0], ctx->stream));
-    LB_LAUNCH(k_kzg_hash, n, LB_KZG_HASH_TPB, (const uint8_t*)b.blobs, (const uint8_t*)b.com, b.z, b.status);
-    LB_LAUNCH(k_kzg_check_com, blocks_for(n), TPB, n, (const uint8_t*)b.com, b.status);
+    LB_TRY(c.stage("kzg_hash"));
+    LB_LAUNCH(k_kzg_hash, n, LB_KZG_HASH_TPB, d_blobs, d_com, d_z, d_st);
+    LB_LAUNCH(k_kzg_check_com, blocks_for(n), TPB, n, d_com, d_st);
   } else {
-    LB_KZG_UP(b.z, z32, (size_t)n * 32);
-    LB_HIP(hipMemsetAsync(b.status, 0, n, ctx->stream));
+    LB_HIP(hipMemsetAsync(d_st, 0, n, ctx->stream));
   }
-  LB_HIP(hipEventRecord(k.ev[1], ctx->stream));
-  LB_LAUNCH(k_kzg_eval, n, LB_KZG_EVAL_TPB, (const uint8_t*)b.blobs, (const fr*)k.d_roots, (const uint8_t*)b.z, b.y,
-            b.status);
-  LB_HIP(hipEventRecord(k.ev[2], ctx->stream));
-  LB_LAUNCH(k_kzg_quotient, n, LB_KZG_EVAL_TPB, (const uint8_t*)b.blobs, (const fr*)k.d_roots, (const uint8_t*)b.z,
-            (const uint8_t*)b.y, (const uint8_t*)b.status, m.quot);
-  LB_HIP(hipEventRecord(k.ev[3], ctx->stream));
-  LB_TRY(kzg_msm(ctx, m, n, m.quot, b.status, LB_KZG_BAD_SCALAR, m.out48));
-  LB_HIP(hipEventRecord(k.ev[4], ctx->stream));
-  LB_HIP(hipMemcpyAsync(out_proofs48, m.out48, (size_t)n * 48, hipMemcpyDeviceToHost, ctx->stream));
-  if (out_y32) LB_HIP(hipMemcpyAsync(out_y32, b.y, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipMemcpyAsync(out_status, b.status, n, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  static const char* const names[] = {"kzg_hash", "kzg_eval", "kzg_quot", "kzg_msm"};
-  return kzg_publish_times(ctx, first, 4 - first, names + first);
+  LB_TRY(c.stage("kzg_eval"));
+  LB_LAUNCH(k_kzg_eval, n, LB_KZG_EVAL_TPB, d_blobs, roots, (const uint8_t*)d_z, d_y, d_st);
+  LB_TRY(c.stage("kzg_quot"));
+  LB_LAUNCH(k_kzg_quotient, n, LB_KZG_EVAL_TPB, d_blobs, roots, (const uint8_t*)d_z, (const uint8_t*)d_y,
+            (const uint8_t*)d_st, d_quot);
+  LB_TRY(c.stage("kzg_msm"));
+  LB_TRY(kzg_msm(ctx, m, n, d_quot, d_st, LB_KZG_BAD_SCALAR, d_out));
+  return c.end();
 }
 
 }  // namespace
@@ -4121,23 +4056,25 @@ int lb_kzg_load_setup_g1(lb_ctx* ctx, const uint8_t* g1_lagrange48, int32_t* out
     return LB_ERR_INVALID_ARGUMENT;
   }
   if (out_bad_index) *out_bad_index = -1;
-  KzgBufs b;
-  LB_TRY(kzg_ensure(ctx, b));
-  KzgMsmBufs m;
-  LB_TRY(kzg_msm_ensure(ctx, m));
+  // the file's points, their statuses, the Jacobian multiples before the inversion
+  std::vector<uint8_t> st(LB_KZG_N);
+  HelperCall c(ctx);
+  auto d_in48 = c.in(g1_lagrange48, (size_t)LB_KZG_N * 48);
+  auto d_pt_st = c.out(st.data(), LB_KZG_N);
+  auto d_J = c.scratch<g1j>(LB_KZG_MSM_ENT);
+  LB_TRY(c.begin());
+  LB_TRY(kzg_ensure(ctx));
   KzgState& k = ctx->kzg;
   // the candidate's table is built beside the loaded one and takes its place only when accepted
   const int cand = k.g1_cur ^ 1;
-  LB_KZG_UP(m.in48, g1_lagrange48, (size_t)LB_KZG_N * 48);
-  LB_HIP(hipEventRecord(k.ev[0], ctx->stream));
-  LB_LAUNCH(k_kzg_setup_g1, blocks_for(LB_KZG_N), TPB, (const uint8_t*)m.in48, m.J, k.d_g1_tab[cand], m.pt_status);
-  LB_HIP(hipEventRecord(k.ev[1], ctx->stream));
-  std::vector<uint8_t> st(LB_KZG_N);
-  LB_HIP(hipMemcpyAsync(st.data(), m.pt_status, LB_KZG_N, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
+  for (DevArray<g1a>& t : k.g1_tab) LB_TRY(t.reserve(ctx, LB_KZG_MSM_ENT, 0));
+  LB_TRY(c.stage("kzg_setup_g1"));
+  LB_LAUNCH(k_kzg_setup_g1, blocks_for(LB_KZG_N), TPB, d_in48, d_J, k.g1_tab[cand].d, d_pt_st);
+  LB_TRY(c.end());
   for (uint32_t i = 0; i < LB_KZG_N; i++) {
     if (st[i] == LB_ST_OK) continue;
     if (out_bad_index) *out_bad_index = (int32_t)i;
+    ctx->n_stages = 0;  // (a refused load publishes no stage)
     ctx->err = "lb_kzg_load_setup_g1: G1 point " + std::to_string(i) + " of the file " +
                (st[i] == LB_ST_NOT_IN_GROUP ? "is not in G1"
                 : st[i] == LB_ST_NOT_ON_CURVE ? "is not on the curve"
@@ -4146,29 +4083,14 @@ int lb_kzg_load_setup_g1(lb_ctx* ctx, const uint8_t* g1_lagrange48, int32_t* out
   }
   k.g1_cur = cand;
   k.g1_loaded = true;
-  static const char* const names[] = {"kzg_setup_g1"};
-  return kzg_publish_times(ctx, 0, 1, names);
+  return LB_OK;
 }
 
 int lb_kzg_g1_lincomb(lb_ctx* ctx, uint32_t n_jobs, const uint8_t* scalars32, uint8_t* out48, uint8_t* out_status) {
   if (!ctx) return LB_ERR_INVALID_ARGUMENT;
   if (n_jobs == 0) return LB_OK;
   LB_TRY(kzg_check_g1_args(ctx, n_jobs, scalars32 && out48 && out_status, "lb_kzg_g1_lincomb"));
-  KzgBufs b;
-  LB_TRY(kzg_ensure(ctx, b));
-  KzgMsmBufs m;
-  LB_TRY(kzg_msm_ensure(ctx, m));
-  KzgState& k = ctx->kzg;
-  LB_KZG_UP(b.blobs, scalars32, (size_t)n_jobs * LB_KZG_BLOB_BYTES);
-  LB_HIP(hipMemsetAsync(b.status, 0, n_jobs, ctx->stream));
-  LB_HIP(hipEventRecord(k.ev[3], ctx->stream));
-  LB_TRY(kzg_msm(ctx, m, n_jobs, b.blobs, b.status, LB_KZG_BAD_SCALAR, m.out48));
-  LB_HIP(hipEventRecord(k.ev[4], ctx->stream));
-  LB_HIP(hipMemcpyAsync(out48, m.out48, (size_t)n_jobs * 48, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipMemcpyAsync(out_status, b.status, n_jobs, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  static const char* const names[] = {"kzg_msm"};
-  return kzg_publish_times(ctx, 3, 1, names);
+  return kzg_lincomb(ctx, n_jobs, scalars32, LB_KZG_BAD_SCALAR, out48, out_status);
 }
 
 int lb_kzg_blob_commitments(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, uint8_t* out_commitments48,
@@ -4176,22 +4098,8 @@ int lb_kzg_blob_commitments(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, uint8
   if (!ctx) return LB_ERR_INVALID_ARGUMENT;
   if (n == 0) return LB_OK;
   LB_TRY(kzg_check_g1_args(ctx, n, blobs && out_commitments48 && out_status, "lb_kzg_blob_commitments"));
-  KzgBufs b;
-  LB_TRY(kzg_ensure(ctx, b));
-  KzgMsmBufs m;
-  LB_TRY(kzg_msm_ensure(ctx, m));
-  KzgState& k = ctx->kzg;
   // a blob is its polynomial's 4096 scalars as the MSM reads them
-  LB_KZG_UP(b.blobs, blobs, (size_t)n * LB_KZG_BLOB_BYTES);
-  LB_HIP(hipMemsetAsync(b.status, 0, n, ctx->stream));
-  LB_HIP(hipEventRecord(k.ev[3], ctx->stream));
-  LB_TRY(kzg_msm(ctx, m, n, b.blobs, b.status, LB_KZG_BAD_BLOB, m.out48));
-  LB_HIP(hipEventRecord(k.ev[4], ctx->stream));
-  LB_HIP(hipMemcpyAsync(out_commitments48, m.out48, (size_t)n * 48, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipMemcpyAsync(out_status, b.status, n, hipMemcpyDeviceToHost, ctx->stream));
-  LB_HIP(hipStreamSynchronize(ctx->stream));
-  static const char* const names[] = {"kzg_msm"};
-  return kzg_publish_times(ctx, 3, 1, names);
+  return kzg_lincomb(ctx, n, blobs, LB_KZG_BAD_BLOB, out_commitments48, out_status);
 }
 
 int lb_kzg_blob_proofs(lb_ctx* ctx, uint32_t n, const uint8_t* blobs, const uint8_t* commitments48,

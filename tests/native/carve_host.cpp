@@ -94,6 +94,12 @@ void cv_sm_layout(unsigned nj, unsigned ns, unsigned rows, int by_index, int agg
   p12[1] = s.pipe2_bytes;
 }
 
+// the capacity a context-owned device array takes for `need` elements when it has `cap`
+unsigned cv_dev_array_cap(unsigned cap, unsigned need, unsigned floor, int doubling) {
+  return dev_array_cap(cap, need, floor, doubling != 0);
+}
+unsigned cv_dev_array_max() { return kDevArrayMax; }
+
 unsigned long long cv_lp_layout(unsigned long long ns, int own_status, unsigned long long start, long long* off) {
   const LpLayout L = layout_lp((size_t)ns, own_status != 0, (size_t)start);
   for (int b = 0; b < LPB_COUNT; b++) off[b] = L.off[b] == kCarveAbsent ? -1 : (long long)L.off[b];
@@ -180,6 +186,14 @@ int main(int argc, char** argv) {
   for (size_t ns : {(size_t)1, (size_t)2, (size_t)896})
     if (lp_ws_bytes(ns) != layout_lp(ns).end || layout_lp(ns, false).end >= layout_lp(ns).end)
       return fail("lp", 0, (unsigned)ns, 0);
+  // the capacity rule: never below the need, unchanged while the array fits, the table's cap
+  for (const bool doubling : {true, false})
+    for (const uint32_t cap : {0u, 1u, 1024u, 4096u, 4097u, 1u << 30, kDevArrayMax, 0xfffffffeu})
+      for (const uint32_t need : {0u, 1u, 1023u, 1024u, 1025u, 4096u, 4097u, (1u << 30) + 1, kDevArrayMax, 0xffffffffu}) {
+        const uint32_t got = dev_array_cap(cap, need, doubling ? 4096u : 1024u, doubling);
+        if (got < need || (need <= cap && got != cap)) return fail("dev_array_cap", cap, need, doubling);
+        if (doubling && need > cap && need <= kDevArrayMax && got > kDevArrayMax) return fail("dev_array_cap max", cap, need, 1);
+      }
   std::printf("ok\n");
   return 0;
 }

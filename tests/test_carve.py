@@ -1,7 +1,8 @@
 """The carving of the host calls' buffers (lodestar_amd/csrc/bls_carve.h) on the host: a g++ build
 of the header behind ctypes (tests/native/carve_host.cpp).  The primitive on random declaration
 lists; the same-message layout over a grid of packages, its sizes restated by hand here; the
-host-buffer call's and the latency path's lists.  A stand-alone build of the same file walks
+host-buffer call's and the latency path's lists; the capacity rule of the context's device arrays
+(dev_array_cap).  A stand-alone build of the same file walks
 the grid under -fsanitize=address,undefined where the host compiler has the runtime."""
 import ctypes
 import itertools
@@ -36,6 +37,8 @@ def lib(tmp_path_factory):
     L.cv_host_layout.restype = ULL
     L.cv_host_layout.argtypes = [ctypes.c_uint, ctypes.c_uint, ULL, ULL, ctypes.c_uint, ctypes.c_int, ctypes.c_int,
                                  ctypes.c_void_p]
+    L.cv_dev_array_cap.restype = L.cv_dev_array_max.restype = ctypes.c_uint
+    L.cv_dev_array_cap.argtypes = [ctypes.c_uint] * 3 + [ctypes.c_int]
     return L
 
 
@@ -201,6 +204,36 @@ def test_lp_ws_bytes_is_the_end_of_run_lps_list(lib, ns):
             assert end <= lib.cv_lp_ws_bytes(ns)
     off = (LL * 9)()
     assert lib.cv_lp_layout(ns, 1, 7, off) == lib.cv_lp_ws_bytes(ns) + 256 and off[0] == 256
+
+
+# ---- the capacity of a context-owned device array ------------------------------------------------
+TABLE, LIST = (4096, 1), (1024, 0)  # (floor, doubling): the pubkey and balance tables; the index lists
+
+
+def test_device_array_capacity(lib):
+    cap = lambda have, need, policy: lib.cv_dev_array_cap(have, need, *policy)  # noqa: E731
+    top = lib.cv_dev_array_max()
+    assert top == 2 ** 31 - 1
+    # the first reservation, below and above the floor
+    assert cap(0, 1, TABLE) == 4096 and cap(0, 5000, TABLE) == 5000
+    assert cap(0, 1, LIST) == 1024 and cap(0, 1025, LIST) == 1025
+    # it fits: no move; one more: a table doubles, a list takes exactly the need
+    assert cap(4096, 4096, TABLE) == 4096 and cap(4096, 4097, TABLE) == 8192
+    assert cap(8192, 20000, TABLE) == 20000  # (more than the double)
+    assert cap(1024, 1024, LIST) == 1024 and cap(1024, 1025, LIST) == 1025 and cap(5000, 5001, LIST) == 5001
+    assert cap(5000, 3, LIST) == 5000  # (a list never shrinks)
+    # a doubling past the table's limit stops at it
+    assert cap(2 ** 30 + 5, 2 ** 30 + 6, TABLE) == top and cap(top - 1, top, TABLE) == top
+    rng = random.Random(7)
+    for _ in range(2000):
+        have = rng.choice((0, 1, 1024, 4096, rng.randrange(2 ** 31), rng.randrange(2 ** 20)))
+        need = rng.choice((0, 1, have, min(have + 1, top), rng.randrange(2 ** 31), rng.randrange(2 ** 20)))
+        for policy in (TABLE, LIST):
+            got = cap(have, need, policy)
+            assert got >= need and (got == have if need <= have else got >= policy[0])
+            if need > have:
+                assert got <= top and (got == max(need, policy[0]) if policy is LIST else
+                                       got == min(max(2 * have, need, 4096), top))
 
 
 def test_standalone_under_sanitizers(tmp_path):
